@@ -20,7 +20,13 @@ main thread to one core after the warm-up (the threads RCCL created keep
 the process's cores); QSMD_BENCH_DEVICE=d pins every rank to GPU d;
 QSMD_LIB_PATH loads another build of libqsmd.so.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W]   (a plain run: set up,
+                                       warm up, time the K steps, one JSON line)
+    python bench.py --full ...        (the plain run's line plus everything
+                                       below that takes runs of its own)
+    python bench.py --dump-outputs DIR ...   (the last timed step's status
+                                       and node count per history and its
+                                       totals, as DIR/<name>.npy)
     torchrun --nproc-per-node N bench.py --gpus N ...   (one rank per GPU)
     python bench.py --early-exit      (BASELINE config 3's early-termination
                                        path: ms to the decision, histories
@@ -29,8 +35,11 @@ QSMD_LIB_PATH loads another build of libqsmd.so.
                                        failure planted at 60 % of the batch:
                                        the geometric rounds and a MIN per round)
 
-Rank 0 prints one JSON line.  At N = 1 it also reports (outside the timed
-region of `value`): the CPU baselines on the host's cores -- the C oracle
+Rank 0 prints one JSON line.  With --full it also reports (outside the timed
+region of `value`) the roofline of the two search kernels, from a leg of
+synchronous calls after the timed region, and at N = 1: the last step's
+verdicts and node counts compared with the oracle's, the CPU baselines on
+the host's cores -- the C oracle
 (oracle/ref_cpu.c, the reference restated with the same semantics) on one
 thread and on every available core, and the literal list transliteration of
 src/Linearisability.hs (the reference-shaped point) on config 1 -- and
@@ -314,6 +323,10 @@ class InFlight:
         nd = self.outs[i][1].cpu().numpy()
         return st, nd, self.totals.numpy(), bi
 
+    def last_totals(self):
+        """The 8 counters the last step's call wrote (this rank's)."""
+        return self.tot[self.steps_run - 1].cpu().numpy()
+
     def close(self):
         for c in self.ctxs:
             c.close()
@@ -322,6 +335,27 @@ class InFlight:
 def device_batch(name, first, n, dev):
     hdr, ev, _ = gen.generate(gen.params(**gen.CONFIGS[name]), first, n, threads=min(16, host_cores()))
     return hdr, ev, torch.from_numpy(hdr.view(np.uint8)).to(dev), torch.from_numpy(ev.view(np.uint8)).to(dev)
+
+
+DUMP_LIMIT = 64_000_000        # bytes --dump-outputs writes at most
+
+
+def dump_outputs(path, st, nd, totals):
+    """The last timed step's outputs as a caller of the hot path receives
+    them: status[n] (float32), nodes[n] (float64; counts below 2^53 are
+    exact), totals[8] (float64).  Past DUMP_LIMIT the per-history arrays are
+    a sample: the sorted indices a generator seeded with 0 draws, written
+    beside them as sample_index.npy."""
+    os.makedirs(path, exist_ok=True)
+    n = len(st)
+    keep = (DUMP_LIMIT - 4096) // (4 + 8 + 8)      # status + nodes + the index, per history
+    if n > keep:
+        idx = np.sort(np.random.default_rng(0).choice(n, size=keep, replace=False))
+        st, nd = st[idx], nd[idx]
+        np.save(os.path.join(path, "sample_index.npy"), idx.astype(np.float64))
+    np.save(os.path.join(path, "status.npy"), np.asarray(st).astype(np.float32))
+    np.save(os.path.join(path, "nodes.npy"), np.asarray(nd).astype(np.float64))
+    np.save(os.path.join(path, "totals.npy"), np.asarray(totals).astype(np.float64))
 
 
 def cpu_baselines(hdr, ev, model_id, target_s, mt_s):
@@ -376,7 +410,7 @@ def reference_shaped(seconds):
 
 
 def early_exit_leg(dev, rank, world, config, n_per_gpu, steps, warmup, chunk, use_dist, host_group, check_oracle,
-                   first_chunk=None, plant=None):
+                   first_chunk=None, plant=None, dump=None):
     """BASELINE config 3's early-termination path: QSMD_FLAG_EARLY_EXIT_BATCH
     over a batch sharded across the ranks (qsmd.dist.check_shard_early_exit_device:
     device-resident shards, one MIN all-reduce of the first failure per
@@ -432,6 +466,8 @@ def early_exit_leg(dev, rank, world, config, n_per_gpu, steps, warmup, chunk, us
            "first_fail": info["first_fail"], "rounds": info["rounds"],
            "totals": dict(zip(("checked", "linearisable", "nonlinearisable", "model_errors", "encode_errors",
                                "budget", "skipped", "nodes"), (int(x) for x in tot)))}
+    if dump and rank == 0:
+        dump_outputs(dump, st.cpu().numpy(), nd.cpu().numpy(), [int(x) for x in tot])
     if check_oracle and world == 1:
         # the oracle on every history up to the first failure; everything after it SKIPPED
         sys.path.insert(0, os.path.join(ROOT, "oracle"))
@@ -497,6 +533,70 @@ def extra_configs(dev, S, knobs, streams):
     return out
 
 
+def roofline_fields(args, n, hdr, nd0, budget_used, roof_s0, roof_hv, roof_call, ms_per_step):
+    """The `roofline` block of the result line, from the roofline leg's
+    per-launch times (InFlight.roofline_leg) and batch 0's node counts."""
+    # roofline, rank-local, of the two kernels that bound a call -- stage 0
+    # and the lane-mode heavy stage -- each SURVEY §8d's algorithmic bytes of
+    # one launch over its mean duration ALONE on the GPU (the roofline leg:
+    # synchronous calls of batch 0 after the timed region, HIP events the
+    # launches record at their start and end; a kernel trace of this command
+    # shows the same launches last).  The top-level fields are the longer
+    # kernel's.  Per history: 16 B header + 16 B per operation + 16 B result
+    # + 16 B per explored node; stage 0 explores min(nodes, budget), the
+    # heavy stage re-reads its histories and explores the nodes past the
+    # budget (the budget the leg's calls ran with, the library's automatic
+    # one included).  Beside them: the same stage-0 bytes per step of the
+    # timed region, and what the PMC counters of a profiled run of the same
+    # configuration and budget give for the same launches.
+    # (budget_used 0xFFFFFFFF: stage 0 ran without a budget -- no heavy stage)
+    heavy = nd0.astype(np.int64) > budget_used
+    n_ev0 = hdr["n_ev"].astype(np.int64)
+    kern = {"stage0": {"kernel": "compact_search<Bank, G32> (stage 0)", "ms": roof_s0,
+                       "alg_bytes_per_launch": alg_bytes(hdr, np.minimum(nd0, budget_used)),
+                       "hbm_io_bytes_per_launch": hbm_bytes(hdr)}}
+    if len(roof_hv) and (roof_hv >= 0).all():
+        kern["heavy"] = {"kernel": "memo_search<Bank> (heavy stage, lane mode)", "ms": roof_hv,
+                         "heavy_histories": int(heavy.sum()),
+                         "alg_bytes_per_launch": int((32 + 8 * n_ev0[heavy]).sum() +
+                                                     16 * (nd0[heavy].astype(np.int64) - budget_used).sum())}
+    pmc = {}
+    if os.path.exists(args.pmc):
+        with open(args.pmc) as f:
+            pmc = json.load(f)
+        if not (pmc.get("config") == args.config and pmc.get("n_hist") == n and
+                pmc.get("stage0_budget") == budget_used):
+            pmc = {}                      # measured on another configuration or budget: not this run's
+    for name, k in kern.items():
+        ms = k.pop("ms")
+        t = float(np.mean(ms)) * 1e-3
+        k["achieved"] = k["alg_bytes_per_launch"] / t / 1e9
+        k["frac"] = k["achieved"] / HBM_PEAK_GBS
+        k["kernel_ms"] = {"mean": float(np.mean(ms)), "median": float(np.median(ms)), "min": float(np.min(ms)),
+                          "launches": int(len(ms))}
+        blk = pmc if name == "stage0" else pmc.get("heavy", {})
+        k["traffic"] = blk.get("hbm_bytes_per_launch") if pmc else None
+        if k["traffic"]:
+            k["hbm_actual"] = k["traffic"] / t / (HBM_PEAK_GBS * 1e9)
+        valu = blk.get("valu_insts_per_launch") if pmc else None
+        if valu:
+            k["valu_issue"] = valu * VALU_CYCLES / (SIMDS * CLOCK_HZ * t)
+    dom = max(kern, key=lambda k: kern[k]["kernel_ms"]["mean"])
+    a_bytes = kern["stage0"]["alg_bytes_per_launch"]
+    roof = {"bound": "hbm", "achieved": kern[dom]["achieved"], "peak": HBM_PEAK_GBS, "unit": "GB/s",
+            "frac": kern[dom]["frac"], "traffic": kern[dom]["traffic"], "kernel": kern[dom]["kernel"],
+            "alg_bytes_per_launch": kern[dom]["alg_bytes_per_launch"], "stage0_budget_used": budget_used,
+            "kernels": kern,
+            "call_ms": {"mean": float(np.mean(roof_call)), "median": float(np.median(roof_call))},
+            "how": "synchronous calls after the timed region, HIP events at each kernel's start and end",
+            "per_step": {"achieved": a_bytes / (ms_per_step * 1e-3) / 1e9,
+                         "frac": a_bytes / (ms_per_step * 1e-3) / 1e9 / HBM_PEAK_GBS,
+                         "how": "stage 0's algorithmic bytes of one launch / ms_per_step (calls in flight)"}}
+    if pmc:
+        roof["pmc_source"] = os.path.relpath(args.pmc, ROOT)
+    return roof
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -504,9 +604,17 @@ def main():
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--config", default="bank_4x16", choices=sorted(gen.CONFIGS))
     ap.add_argument("--n-hist", type=int, default=1_000_000, help="histories per GPU")
+    ap.add_argument("--full", action="store_true",
+                    help="also everything beside the headline that takes runs of its own: the roofline leg, the "
+                         "oracle's check of the last step, the CPU baselines, the extra BASELINE configs "
+                         "(--early-exit: the oracle's check)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps write the last step's outputs (rank 0's) as DIR/<name>.npy: status "
+                         "(float32) and nodes (float64) per history, totals (float64, the step's 8 counters); a "
+                         "seeded sample of the histories (sample_index.npy) past 64 MB")
     ap.add_argument("--cpu-seconds", type=float, default=10.0)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra", action="store_true", help="skip the extra BASELINE configs")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the oracle and the CPU baselines")
+    ap.add_argument("--no-extra", action="store_true", help="--full without the extra BASELINE configs")
     ap.add_argument("--stage0-budget", type=int, default=None,
                     help="stage-0 node budget (default 20 with calls in flight, the library's otherwise)")
     ap.add_argument("--param", action="append", default=[], metavar="NAME=VALUE",
@@ -609,8 +717,8 @@ def main():
         if args.plant is not None and args.config == "bank_4x16":
             config = "bank_4x16"             # (a linearisable stream: the planted failure is its only one)
         ee = early_exit_leg(dev, rank, world, config, n_ee, args.steps, args.warmup, args.chunk, use_dist, host_group,
-                            rank == 0 and not args.no_cpu_baseline, first_chunk=args.first_chunk or None,
-                            plant=args.plant)
+                            rank == 0 and args.full and not args.no_cpu_baseline,
+                            first_chunk=args.first_chunk or None, plant=args.plant, dump=args.dump_outputs)
         if rank == 0:
             out = {"metric": "histories searched/sec up to the batch's decision, early-termination path "
                              "(QSMD_FLAG_EARLY_EXIT_BATCH, sharded); ms_to_decision beside it",
@@ -683,8 +791,11 @@ def main():
     elapsed = run.timed(args.steps, args.warmup)
     s0_ms, call_ms = run.ctxs[0].timing_read()
     st, nd, tot, last_batch = run.results()
-    roof_s0, roof_hv, roof_call, budget_used = run.roofline_leg(max(1, args.roof_calls))
-    nd0 = run.outs[0][1].cpu().numpy()             # batch 0's node counts (the roofline leg's calls)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, st, nd, run.last_totals())
+    if args.full:
+        roof_s0, roof_hv, roof_call, budget_used = run.roofline_leg(max(1, args.roof_calls))
+        nd0 = run.outs[0][1].cpu().numpy()         # batch 0's node counts (the roofline leg's calls)
     fold = run.ctxs[0].get_param("fold")
     run.close()
 
@@ -693,65 +804,6 @@ def main():
     value = total_hist * args.steps / elapsed
     nodes_total = int(tot[7])                      # every timed step, every rank
     assert int(tot[0]) + int(tot[4]) + int(tot[5]) == total_hist * args.steps, tot
-
-    # roofline, rank-local, of the two kernels that bound a call -- stage 0
-    # and the lane-mode heavy stage -- each SURVEY §8d's algorithmic bytes of
-    # one launch over its mean duration ALONE on the GPU (the roofline leg:
-    # synchronous calls of batch 0 after the timed region, HIP events the
-    # launches record at their start and end; a kernel trace of this command
-    # shows the same launches last).  The top-level fields are the longer
-    # kernel's.  Per history: 16 B header + 16 B per operation + 16 B result
-    # + 16 B per explored node; stage 0 explores min(nodes, budget), the
-    # heavy stage re-reads its histories and explores the nodes past the
-    # budget (the budget the leg's calls ran with, the library's automatic
-    # one included).  Beside them: the same stage-0 bytes per step of the
-    # timed region, and what the PMC counters of a profiled run of the same
-    # configuration and budget give for the same launches.
-    # (budget_used 0xFFFFFFFF: stage 0 ran without a budget -- no heavy stage)
-    heavy = nd0.astype(np.int64) > budget_used
-    n_ev0 = hdr["n_ev"].astype(np.int64)
-    kern = {"stage0": {"kernel": "compact_search<Bank, G32> (stage 0)", "ms": roof_s0,
-                       "alg_bytes_per_launch": alg_bytes(hdr, np.minimum(nd0, budget_used)),
-                       "hbm_io_bytes_per_launch": hbm_bytes(hdr)}}
-    if len(roof_hv) and (roof_hv >= 0).all():
-        kern["heavy"] = {"kernel": "memo_search<Bank> (heavy stage, lane mode)", "ms": roof_hv,
-                         "heavy_histories": int(heavy.sum()),
-                         "alg_bytes_per_launch": int((32 + 8 * n_ev0[heavy]).sum() +
-                                                     16 * (nd0[heavy].astype(np.int64) - budget_used).sum())}
-    pmc = {}
-    if os.path.exists(args.pmc):
-        with open(args.pmc) as f:
-            pmc = json.load(f)
-        if not (pmc.get("config") == args.config and pmc.get("n_hist") == n and
-                pmc.get("stage0_budget") == budget_used):
-            pmc = {}                      # measured on another configuration or budget: not this run's
-    for name, k in kern.items():
-        ms = k.pop("ms")
-        t = float(np.mean(ms)) * 1e-3
-        k["achieved"] = k["alg_bytes_per_launch"] / t / 1e9
-        k["frac"] = k["achieved"] / HBM_PEAK_GBS
-        k["kernel_ms"] = {"mean": float(np.mean(ms)), "median": float(np.median(ms)), "min": float(np.min(ms)),
-                          "launches": int(len(ms))}
-        blk = pmc if name == "stage0" else pmc.get("heavy", {})
-        k["traffic"] = blk.get("hbm_bytes_per_launch") if pmc else None
-        if k["traffic"]:
-            k["hbm_actual"] = k["traffic"] / t / (HBM_PEAK_GBS * 1e9)
-        valu = blk.get("valu_insts_per_launch") if pmc else None
-        if valu:
-            k["valu_issue"] = valu * VALU_CYCLES / (SIMDS * CLOCK_HZ * t)
-    dom = max(kern, key=lambda k: kern[k]["kernel_ms"]["mean"])
-    a_bytes = kern["stage0"]["alg_bytes_per_launch"]
-    roof = {"bound": "hbm", "achieved": kern[dom]["achieved"], "peak": HBM_PEAK_GBS, "unit": "GB/s",
-            "frac": kern[dom]["frac"], "traffic": kern[dom]["traffic"], "kernel": kern[dom]["kernel"],
-            "alg_bytes_per_launch": kern[dom]["alg_bytes_per_launch"], "stage0_budget_used": budget_used,
-            "kernels": kern,
-            "call_ms": {"mean": float(np.mean(roof_call)), "median": float(np.median(roof_call))},
-            "how": "synchronous calls after the timed region, HIP events at each kernel's start and end",
-            "per_step": {"achieved": a_bytes / (ms_per_step * 1e-3) / 1e9,
-                         "frac": a_bytes / (ms_per_step * 1e-3) / 1e9 / HBM_PEAK_GBS,
-                         "how": "stage 0's algorithmic bytes of one launch / ms_per_step (calls in flight)"}}
-    if pmc:
-        roof["pmc_source"] = os.path.relpath(args.pmc, ROOT)
 
     out = {
         "metric": METRIC, "value": value, "unit": "histories/s", "n_gpus": world,
@@ -787,14 +839,15 @@ def main():
                      "linearisable": int(tot[1]), "nonlinearisable": int(tot[2]),
                      "model_errors": int(tot[3]), "budget": int(tot[5])},
         "device_ms": {"in_flight": {"stage0_mean": float(np.mean(s0_ms)) if len(s0_ms) else None,
-                                    "call_mean": float(np.mean(call_ms)) if len(call_ms) else None},
-                      "alone": {"stage0_mean": float(np.mean(roof_s0)),
-                                "heavy_mean": float(np.mean(roof_hv)) if len(roof_hv) else None,
-                                "call_mean": float(np.mean(roof_call))}},
-        "roofline": roof,
+                                    "call_mean": float(np.mean(call_ms)) if len(call_ms) else None}},
         "cpu_baseline": None,
     }
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full:
+        out["device_ms"]["alone"] = {"stage0_mean": float(np.mean(roof_s0)),
+                                     "heavy_mean": float(np.mean(roof_hv)) if len(roof_hv) else None,
+                                     "call_mean": float(np.mean(roof_call))}
+        out["roofline"] = roofline_fields(args, n, hdr, nd0, budget_used, roof_s0, roof_hv, roof_call, ms_per_step)
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         # the oracle over the last step's batch: the CPU baseline's timing and the check
         hdr_l, ev_l = host_batches[last_batch]
         cb, st_o, nd_o = cpu_baselines(hdr_l, ev_l, model_id, args.cpu_seconds, 2.0)
@@ -806,7 +859,7 @@ def main():
             out["mismatches_vs_oracle"] = int(((st_o != st) | (nd_o != nd.astype(np.uint64))).sum())
         out["checked_vs_oracle"] = len(hdr_l)
         out["checked_batch"] = last_batch
-    if rank == 0 and world == 1 and not args.no_extra:
+    if args.full and rank == 0 and world == 1 and not args.no_extra:
         s_x = min(S, 3) if args.inflight <= 0 else S
         out["extra"] = {"configs": extra_configs(dev, s_x, knobs, streams[:s_x])}
     if rank == 0:

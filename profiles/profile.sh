@@ -6,13 +6,13 @@
 #   3. --pmc WRITE_SIZE                   HBM write bytes  (own pass)
 #   4. --pmc SQ_* (two passes)            waves, busy/wait cycles, VALU/LDS
 # then profiles/summarize_pmc.py writes <out_dir>/summary.json over the last
-# 30 stage-0 dispatches: bench.py's roofline leg (30 synchronous calls after
-# its timed region), the launches its roofline.kernel_ms times.
+# 30 stage-0 dispatches: bench.py --full's roofline leg (30 synchronous calls
+# after its timed region), the launches its roofline.kernel_ms times.
 # Every pass has its own time limit; a pass that times out, aborts or
 # crashes stops the script (nothing further runs on the GPU).
 OUT=${1:-gpurun_out/prof}
 shift || true
-ARGS=${@:-"--steps 20 --warmup 5 --no-cpu-baseline --no-extra"}
+ARGS=${@:-"--full --steps 20 --warmup 5 --no-cpu-baseline --no-extra"}
 export TMPDIR=/tmp
 mkdir -p "$OUT"
 run() {  # name, rocprofv3 args...

@@ -217,7 +217,7 @@ def test_bench_two_ranks_on_one_gpu():
     env = dict(os.environ, QSMD_BENCH_DEVICE="0", QSMD_BENCH_COUNTERS="gloo", PYTHONUNBUFFERED="1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", str(_free_port()), "bench.py", "--gpus", "2",
-           "--steps", "6", "--warmup", "2", "--n-hist", "20000", "--rotate", "3", "--no-extra",
+           "--steps", "6", "--warmup", "2", "--n-hist", "20000", "--rotate", "3", "--full", "--no-extra",
            "--no-cpu-baseline", "--roof-calls", "2"]
     p = subprocess.run(cmd, cwd=root, env=env, capture_output=True, text=True, timeout=240)
     assert p.returncode == 0, p.stderr[-3000:]

@@ -758,7 +758,7 @@ def test_bench_knobs_in_flight_full_size(name, n):
     context's tail grids and lane tables come from another batch's call), on
     config 2 (1M per batch) and on config 3's per-GPU share of 10M over 8 GPUs
     (1.25M): every status and node count of every call equals the oracle's
-    (/root/reference/test/Bank.hs:256-287 checks one history per call)."""
+    (the reference's test/Bank.hs:256-287 checks one history per call)."""
     torch = pytest.importorskip("torch")
     S, K, steps = 4, 5, 10
     mid = gen.CONFIGS[name]["model_id"]

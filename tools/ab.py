@@ -23,8 +23,8 @@ def main():
     for r in range(rounds):
         for lib in (libs if r % 2 == 0 else libs[::-1]):
             env = dict(os.environ, QSMD_LIB_PATH=os.path.abspath(lib))
-            out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--no-cpu-baseline", "--no-extra",
-                                  *extra], env=env, capture_output=True, text=True, timeout=300)
+            out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--no-cpu-baseline",
+                                  "--no-extra", *extra], env=env, capture_output=True, text=True, timeout=300)
             if out.returncode != 0:
                 print(out.stderr[-2000:], file=sys.stderr)
                 sys.exit(out.returncode)
