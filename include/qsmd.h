@@ -109,6 +109,53 @@ typedef struct qsmd_bank_model {
     int64_t  balance[QSMD_BANK_MAX_ACCOUNTS];  /* int32 range; 0 if absent  */
 } qsmd_bank_model;
 
+/* Table-driven model: ANY finite-state model, given as tables at run time
+ * (no recompile).  The reference's `linearisable` takes arbitrary
+ * transition / postcondition closures (src/Linearisability.hs:52-58); a C ABI
+ * cannot, but a model with at most QSMD_TABLE_MAX_STATES states whose
+ * invocations and responses are at most 32 symbols each is four tables.  A
+ * step from state s with invocation symbol i and response symbol r is, as
+ * src/Linearisability.hs:63-65:
+ *     postcondition = bit r of post[s][i]
+ *     next state    = on_resp[on_inv[s][i]][r]
+ * An event's symbol is its `code` byte; a, b and val are ignored.  Limits:
+ * 256 states, 32 invocation symbols, 32 response symbols, and as for every
+ * model 128 events and 128 pids per history (pids may share events freely).
+ *
+ * qsmd_check_batch / qsmd_check_batch_device with QSMD_MODEL_TABLE:
+ *   - model0: NULL = init_state, else a pointer to a uint32_t state, which
+ *     must be < n_states (QSMD_ERR_ARG otherwise); no table set: QSMD_ERR_ARG;
+ *   - QSMD_FLAG_EXHAUSTIVE, QSMD_FLAG_WITNESS and max_nodes as for the other
+ *     models; QSMD_FLAG_MEMO is accepted and changes nothing (counts stay
+ *     exact); QSMD_FLAG_EARLY_EXIT_BATCH, qsmd_split_frontier and
+ *     qsmd_check_tasks return QSMD_ERR_UNSUPPORTED;
+ *   - per history QSMD_STATUS_ENCODE_ERROR, with no search: hdr.model_id !=
+ *     3, an invocation code >= n_inv, a response code >= n_resp, n_ev > 128,
+ *     ev_off + n_ev > n_events;
+ *   - totals and the time limit (qsmd_set_time_limit_ms, qsmd_timed_out) as
+ *     for the other models.
+ * Knob "table_budget" (default 256; qsmd_get_param reads it): histories are
+ * searched in two passes per width class (<= 32, <= 64, <= 128 events), the
+ * first with this node budget; a search over it runs again from the root in
+ * the second, 64 to a wavefront, so a few long searches do not each hold 63
+ * idle lanes.  0 = a single pass.  Results are unchanged.  qsmd_get_param
+ * "table_pass2_last": histories the second pass took in the most recent
+ * table call (waits for it).  The cascade's knobs, qsmd_probe_read and the
+ * timing ring (qsmd_last_kernel_ms, qsmd_timing_read) do not apply to table
+ * calls. */
+#define QSMD_MODEL_TABLE 3u
+#define QSMD_TABLE_MAX_STATES 256
+#define QSMD_TABLE_MAX_INV     32
+#define QSMD_TABLE_MAX_RESP    32
+typedef struct qsmd_table_model {
+    uint32_t n_states, n_inv, n_resp, init_state;
+    const uint8_t*  on_inv;    /* [n_states][n_inv]  transition m (Left inv)   */
+    const uint8_t*  on_resp;   /* [n_states][n_resp] transition m (Right resp) */
+    const uint32_t* post;      /* [n_states][n_inv]  bit r: postcondition m inv r */
+    const uint32_t* post_err;  /* same shape, may be NULL; bit r: the postcondition
+                                  raises -> QSMD_STATUS_MODEL_ERROR (wins over post) */
+} qsmd_table_model;
+
 /* -------------------------------------------------------------- results */
 
 #define QSMD_STATUS_NONLINEARISABLE 0u  /* linearisable ... == False        */
@@ -161,6 +208,15 @@ int  qsmd_open(qsmd_ctx** out, int device);
 void qsmd_close(qsmd_ctx* ctx);
 const char* qsmd_last_error(const qsmd_ctx* ctx);
 uint32_t qsmd_abi_version(void);
+
+/* Set the context's table model (one per context; a second call replaces
+ * it).  Host pointers; the tables are copied, the context owns the device
+ * copy and frees it in qsmd_close.  Everything the kernel will index is
+ * checked: dimensions non-zero and within the maxima, every on_inv / on_resp
+ * entry and init_state < n_states, on_inv / on_resp / post non-NULL --
+ * otherwise QSMD_ERR_ARG, and the context keeps its previous table.  Waits
+ * for the context's last call. */
+int qsmd_table_set(qsmd_ctx* ctx, const qsmd_table_model* model);
 
 /* Threading and streams.  Every entry point of one context serialises on the
  * context's mutex, and the check calls of one context are ordered: a call on
@@ -301,7 +357,7 @@ int qsmd_set_stage0_budget(qsmd_ctx* ctx, uint64_t nodes);
  *                       workgroup that gave up waiting is BUDGET) */
 int qsmd_set_param(qsmd_ctx* ctx, const char* name, uint64_t value);
 
-/* Read a knob ("stage0_budget": 0 while automatic, "stage0w_budget_auto", "fold",
+/* Read a knob ("table_budget", "stage0_budget": 0 while automatic, "stage0w_budget_auto", "fold",
  * "heavy_mode", "memo_after", "resume_cap", "tail_cap", "tail_min", "heavy_buckets") or
  * "stage0_budget_last": the stage-0 budget the most recent
  * finished check call ran with (the automatic one included; waits for the

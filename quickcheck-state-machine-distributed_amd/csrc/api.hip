@@ -163,6 +163,15 @@ struct qsmd_ctx {
     // split-search entry points: their own device buffers
     char* sx = nullptr;
     size_t sx_bytes = 0;
+    // QSMD_MODEL_TABLE (csrc/table.hip): the device copy of the table set by
+    // qsmd_table_set (one per context), its initial state, pass 1's node
+    // budget, and the table path's own workspace (header, class and heavy lists)
+    uint32_t* tab_blob = nullptr;
+    TableDev tab{};
+    uint32_t tab_init = 0;
+    uint64_t table_budget = 256;
+    char* tws = nullptr;
+    size_t tws_bytes = 0;
     uint8_t* wf_rank_host = nullptr;   // wellformed: pid rank table (pinned) and its device copy
     char* wf_rank_dev = nullptr;
     size_t wf_rank_bytes = 0;
@@ -371,6 +380,8 @@ void qsmd_close(qsmd_ctx* c) {
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     if (c->ws) (void)hipFree(c->ws);
     if (c->sx) (void)hipFree(c->sx);
+    if (c->tab_blob) (void)hipFree(c->tab_blob);
+    if (c->tws) (void)hipFree(c->tws);
     if (c->mt) (void)hipFree(c->mt);
     if (c->rs) (void)hipFree(c->rs);
     if (c->xm) (void)hipFree(c->xm);
@@ -485,6 +496,8 @@ int qsmd_set_param(qsmd_ctx* c, const char* name, uint64_t value) {
     } else if (n == "fold") {
         if (value > 1) return fail(c, QSMD_ERR_ARG, "fold: 0 or 1");
         c->fold = value;
+    } else if (n == "table_budget") {       // QSMD_MODEL_TABLE: pass 1's node budget (0 = a single pass)
+        c->table_budget = value;
     } else if (n == "heavy_mode") {
         if (value > 2) return fail(c, QSMD_ERR_ARG, "heavy_mode: 0 = wave, 1 = lane, 2 = auto");
         c->heavy_mode = value;
@@ -530,6 +543,52 @@ int qsmd_set_memo_capacity(qsmd_ctx* c, uint64_t entries) {
 int qsmd_set_stage0_grid(qsmd_ctx* c, uint64_t max_blocks) {
     if (!c || max_blocks == 0 || max_blocks > 0x7FFFFFFFull) return QSMD_ERR_ARG;
     c->stage0_max_grid = max_blocks;
+    return QSMD_OK;
+}
+
+int qsmd_table_set(qsmd_ctx* c, const qsmd_table_model* m) {
+    if (!c) return QSMD_ERR_ARG;
+    std::lock_guard<std::mutex> g(c->mu);
+    if (!m || !m->on_inv || !m->on_resp || !m->post) return fail(c, QSMD_ERR_ARG, "qsmd_table_set: null table");
+    if (m->n_states == 0 || m->n_states > QSMD_TABLE_MAX_STATES || m->n_inv == 0 || m->n_inv > QSMD_TABLE_MAX_INV ||
+        m->n_resp == 0 || m->n_resp > QSMD_TABLE_MAX_RESP)
+        return fail(c, QSMD_ERR_ARG, "qsmd_table_set: dimensions outside 1..256 states, 1..32 symbols");
+    if (m->init_state >= m->n_states) return fail(c, QSMD_ERR_ARG, "qsmd_table_set: init_state >= n_states");
+    const uint32_t si = m->n_states * m->n_inv, sr = m->n_states * m->n_resp;
+    for (uint32_t k = 0; k < si; ++k)
+        if (m->on_inv[k] >= m->n_states) return fail(c, QSMD_ERR_ARG, "qsmd_table_set: on_inv entry >= n_states");
+    for (uint32_t k = 0; k < sr; ++k)
+        if (m->on_resp[k] >= m->n_states) return fail(c, QSMD_ERR_ARG, "qsmd_table_set: on_resp entry >= n_states");
+    TableDev t{};
+    t.n_states = m->n_states;
+    t.n_inv = m->n_inv;
+    t.n_resp = m->n_resp;
+    t.has_err = m->post_err ? 1u : 0u;
+    t.blob_words = table_words(t);
+    // (bits at or above n_resp are never read: the kernel checks every code)
+    std::vector<uint32_t> blob(t.blob_words, 0u);
+    std::memcpy(blob.data(), m->post, (size_t)si * 4);
+    if (m->post_err) std::memcpy(blob.data() + table_off_err(t), m->post_err, (size_t)si * 4);
+    std::memcpy(blob.data() + table_off_inv(t), m->on_inv, si);
+    std::memcpy(blob.data() + table_off_resp(t), m->on_resp, sr);
+    HIP_TRY(c, hipSetDevice(c->device), "hipSetDevice");
+    uint32_t* dev = nullptr;
+    hipError_t e = hipMalloc(reinterpret_cast<void**>(&dev), (size_t)t.blob_words * 4);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(c, QSMD_ERR_NOMEM, "hipMalloc", e);
+    }
+    e = hipMemcpy(dev, blob.data(), (size_t)t.blob_words * 4, hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        (void)hipFree(dev);
+        return fail(c, QSMD_ERR_DEVICE, "H2D table", e);
+    }
+    quiesce(c);                         // the last call may still read the old table
+    if (c->tab_blob) (void)hipFree(c->tab_blob);
+    t.blob = dev;
+    c->tab_blob = dev;
+    c->tab = t;
+    c->tab_init = m->init_state;
     return QSMD_OK;
 }
 
@@ -649,10 +708,89 @@ static WaveArgs wave_args(const qsmd_ctx* c, const SearchArgs& a, uint32_t flags
     return wp;
 }
 
+// route of a QSMD_MODEL_TABLE call (the host entry, from the headers): the
+// width classes present (bits 0..2) under kClassesKnown; else every class
+enum : uint32_t { kClassesKnown = 8u };
+
+// One QSMD_MODEL_TABLE call (csrc/table.hip): the binning kernel, per width
+// class pass 1 and (with a budget) pass 2, the totals -- on one stream, no
+// host round trip.  The cascade's workspace and knobs are not touched.
+static int check_table_locked(qsmd_ctx* c, const qsmd_hdr* hdr, uint64_t n_hist, const qsmd_event* events,
+                              uint64_t n_events, const void* model0, uint32_t flags, uint64_t max_nodes,
+                              uint8_t* status, uint64_t* nodes, uint8_t* witness, qsmd_totals* totals,
+                              hipStream_t s, uint32_t route) {
+    if (flags & QSMD_FLAG_EARLY_EXIT_BATCH)
+        return fail(c, QSMD_ERR_UNSUPPORTED, "QSMD_FLAG_EARLY_EXIT_BATCH: not for QSMD_MODEL_TABLE");
+    if (!c->tab_blob) return fail(c, QSMD_ERR_ARG, "QSMD_MODEL_TABLE: no table set (qsmd_table_set)");
+    if (n_hist && (!hdr || !status)) return fail(c, QSMD_ERR_ARG, "null hdr/status");
+    if (n_hist > 0xFFFFFFFFull) return fail(c, QSMD_ERR_ARG, "n_hist > 2^32-1");
+    const uint32_t state0 = model0 ? *static_cast<const uint32_t*>(model0) : c->tab_init;
+    if (state0 >= c->tab.n_states) return fail(c, QSMD_ERR_ARG, "model0: state >= n_states");
+    HIP_TRY(c, hipSetDevice(c->device), "hipSetDevice");
+    HIP_TRY(c, order_after_previous(c, s), "order after the previous call");
+
+    const size_t lst = align_up(n_hist * 4 + 4);
+    const size_t off_tot = kTabHeader + 6 * lst;
+    int rc = grow(c, &c->tws, &c->tws_bytes, off_tot + align_up(sizeof(qsmd_totals)));
+    if (rc) return rc;
+    HIP_TRY(c, hipMemsetAsync(c->tws, 0, kTabHeader, s), "memset header");
+    TableArgs p{};
+    p.s.hdr = hdr;
+    p.s.events = reinterpret_cast<const uint2*>(events);
+    p.s.n_hist = n_hist;
+    p.s.n_events = n_events;
+    p.s.flags = flags;
+    p.s.model_id = QSMD_MODEL_TABLE;
+    p.s.max_nodes = max_nodes;
+    p.s.time_limit = c->time_limit_ms * 100000ull;   // 100 MHz s_memrealtime
+    p.s.status = status;
+    p.s.nodes = nodes;
+    p.s.witness = (flags & QSMD_FLAG_WITNESS) ? witness : nullptr;
+    p.s.buckets = reinterpret_cast<unsigned long long*>(c->tws + kTabOffBuckets);
+    p.cnt = reinterpret_cast<uint32_t*>(c->tws);
+    p.s.timed_out = p.cnt + TC_TIMED;
+    p.t = c->tab;
+    p.state0 = state0;
+    for (int k = 0; k < 3; ++k) {
+        p.class_list[k] = reinterpret_cast<uint32_t*>(c->tws + kTabHeader + (size_t)k * lst);
+        p.heavy_list[k] = reinterpret_cast<uint32_t*>(c->tws + kTabHeader + (size_t)(3 + k) * lst);
+    }
+    p.budget = c->table_budget;
+    p.totals = totals ? totals : reinterpret_cast<qsmd_totals*>(c->tws + off_tot);
+    p.probe_host = c->probe_host;
+    // grids: every kernel is grid-stride over a count read on the device, so
+    // any grid gives the same results.  One workgroup per group of 64 while
+    // the tables are small (each workgroup copies them to LDS), else a few per
+    // CU; pass 2 from the last table call's count.
+    const uint64_t groups = std::max<uint64_t>((n_hist + 63) / 64, 1);
+    const uint64_t cap1 = (size_t)c->tab.blob_words * 4 <= 4096 ? 65536ull : 8ull * c->n_cu;
+    const uint64_t last2 = c->probe_host[kProbeTabPass2];
+    // (at least 16 per CU: a workgroup with no group to search returns at
+    // once, and the first call has no count -- on 256 workgroups its pass 2
+    // took 119 ms against 22 ms, profiles/table/kernel_trace.csv)
+    const uint64_t g2 = std::min<uint64_t>(std::min<uint64_t>(groups, cap1),
+                                           std::max<uint64_t>((last2 + last2 / 4 + 63) / 64, 16ull * c->n_cu));
+    uint32_t grid1[3], grid2[3];
+    for (int k = 0; k < 3; ++k) {
+        grid1[k] = (uint32_t)std::min<uint64_t>(groups, cap1);
+        grid2[k] = (uint32_t)g2;
+    }
+    HIP_TRY(c, launch_table(p, grid1, grid2, (route & kClassesKnown) ? (route & 7u) : 7u, s), "table launch");
+    const bool own = s == c->stream;
+    if (!own) HIP_TRY(c, hipEventRecord(c->done_ev, s), "hipEventRecord");
+    c->done_last = !own;
+    c->last_stream = s;
+    c->in_flight = true;
+    return QSMD_OK;
+}
+
 static int check_device_locked(qsmd_ctx* c, uint32_t model_id, const qsmd_hdr* hdr, uint64_t n_hist,
                                const qsmd_event* events, uint64_t n_events, const void* model0,
                                uint32_t flags, uint64_t max_nodes, uint8_t* status, uint64_t* nodes,
                                uint8_t* witness, qsmd_totals* totals, hipStream_t s, uint32_t route = 0u) {
+    if (model_id == QSMD_MODEL_TABLE)
+        return check_table_locked(c, hdr, n_hist, events, n_events, model0, flags, max_nodes, status, nodes,
+                                  witness, totals, s, route);
     if (model_id != QSMD_MODEL_BANK && model_id != QSMD_MODEL_TICKET)
         return fail(c, QSMD_ERR_ARG, "unknown model_id");
     if (n_hist && (!hdr || !status)) return fail(c, QSMD_ERR_ARG, "null hdr/status");
@@ -1106,7 +1244,12 @@ int qsmd_check_batch(qsmd_ctx* c, uint32_t model_id, const qsmd_hdr* hdr, uint64
         fits0 = fits0 || (few && hdr[i].n_ev <= 32u);
         fits0w = fits0w || (few && hdr[i].n_ev <= 64u);
     }
-    const uint32_t route = n_hist == 0 ? 0u : (fits0 ? 0u : kSkip0) | (fits0w || fits0 ? 0u : kSkip0w);
+    uint32_t route = n_hist == 0 ? 0u : (fits0 ? 0u : kSkip0) | (fits0w || fits0 ? 0u : kSkip0w);
+    if (model_id == QSMD_MODEL_TABLE) {     // the width classes present: one launch per non-empty class
+        route = kClassesKnown;
+        for (uint64_t i = 0; i < n_hist && (route & 7u) != 7u; ++i)
+            route |= hdr[i].n_ev <= 32u ? 1u : (hdr[i].n_ev <= 64u ? 2u : 4u);
+    }
     rc = check_device_locked(c, model_id, d_hdr, n_hist, d_ev, n_events, model0, flags, max_nodes, d_st, d_nd,
                              want_w ? d_w : nullptr, d_tot, s, route);
     if (rc) {
@@ -1282,6 +1425,11 @@ int qsmd_get_param(qsmd_ctx* c, const char* name, uint64_t* out) {
         *out = c->tail_min;
     } else if (n == "heavy_buckets") {
         *out = c->heavy_buckets;
+    } else if (n == "table_budget") {
+        *out = c->table_budget;
+    } else if (n == "table_pass2_last") {    // histories pass 2 took in the most recent QSMD_MODEL_TABLE call
+        quiesce(c);
+        *out = c->probe_host[kProbeTabPass2];
     } else {
         return fail(c, QSMD_ERR_ARG, "unknown parameter");
     }
@@ -1319,6 +1467,7 @@ int qsmd_split_frontier(qsmd_ctx* c, uint32_t model_id, const qsmd_hdr* hdr, con
     if (!c) return QSMD_ERR_ARG;
     if (!hdr || !fr || (max_tasks && !tasks_out) || (n_events && !events))
         return fail(c, QSMD_ERR_ARG, "null argument");
+    if (model_id == QSMD_MODEL_TABLE) return fail(c, QSMD_ERR_UNSUPPORTED, "split search: not for QSMD_MODEL_TABLE");
     if (model_id != QSMD_MODEL_BANK && model_id != QSMD_MODEL_TICKET) return fail(c, QSMD_ERR_ARG, "unknown model_id");
     if (max_tasks > (1ull << 24)) return fail(c, QSMD_ERR_ARG, "max_tasks > 2^24");
     std::lock_guard<std::mutex> g(c->mu);
@@ -1396,6 +1545,7 @@ int qsmd_check_tasks(qsmd_ctx* c, uint32_t model_id, const qsmd_hdr* hdr, const 
     if (!c) return QSMD_ERR_ARG;
     if (!hdr || (n_tasks && (!tasks || !status_out)) || (n_events && !events))
         return fail(c, QSMD_ERR_ARG, "null argument");
+    if (model_id == QSMD_MODEL_TABLE) return fail(c, QSMD_ERR_UNSUPPORTED, "split search: not for QSMD_MODEL_TABLE");
     if (model_id != QSMD_MODEL_BANK && model_id != QSMD_MODEL_TICKET) return fail(c, QSMD_ERR_ARG, "unknown model_id");
     if (n_tasks > (1ull << 24)) return fail(c, QSMD_ERR_ARG, "n_tasks > 2^24");
     if (hdr->model_id != model_id || !split_hdr_ok(hdr, n_events)) return fail(c, QSMD_ERR_ARG, "bad history header");

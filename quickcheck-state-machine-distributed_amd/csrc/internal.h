@@ -364,6 +364,65 @@ hipError_t launch_gen(const qsmd_gen_params& p, uint64_t first, uint64_t n_hist,
 hipError_t launch_wellformed(const qsmd_hdr* hdr, uint64_t n_hist, const uint2* events, uint64_t n_events,
                              const uint8_t* rank, qsmd_wf* out, uint32_t grid, hipStream_t s);
 
+// ------------------------------------------------------------ table models
+// QSMD_MODEL_TABLE (csrc/table.hip): a finite-state model given as tables at
+// run time.  The context's device copy is one blob of 32-bit words, copied
+// as it is into LDS by every workgroup:
+//   post [n_states * n_inv] u32 | post_err (the same, when given) |
+//   on_inv [n_states * n_inv] u8 | on_resp [n_states * n_resp] u8
+// (each byte table padded to a whole word, the blob to 16 bytes).
+struct TableDev {
+    const uint32_t* blob;         // device
+    uint32_t blob_words;          // a multiple of 4
+    uint32_t n_states, n_inv, n_resp;
+    uint32_t has_err;             // post_err present
+};
+// word offsets into the blob
+__host__ __device__ inline uint32_t table_off_err(const TableDev& t) { return t.n_states * t.n_inv; }
+__host__ __device__ inline uint32_t table_off_inv(const TableDev& t) {
+    return (t.has_err ? 2u : 1u) * t.n_states * t.n_inv;
+}
+__host__ __device__ inline uint32_t table_off_resp(const TableDev& t) {
+    return table_off_inv(t) + (t.n_states * t.n_inv + 3u) / 4u;
+}
+__host__ __device__ inline uint32_t table_words(const TableDev& t) {
+    return (table_off_resp(t) + (t.n_states * t.n_resp + 3u) / 4u + 3u) / 4u * 4u;
+}
+
+// The table path's own workspace header: counters (u32), then the totals'
+// buckets (kBuckets x kBucketWords u64, as the cascade's).
+enum TCnt : uint32_t {
+    TC_CLASS = 0,       // histories per width class (32 / 64 / 128 events): 3 counters
+    TC_HEAVY = 3,       // histories over the pass-1 budget, per class: 3 counters
+    TC_TIMED = 6,       // the time limit fired
+    TC_N = 16
+};
+constexpr size_t kTabOffBuckets = 256;
+constexpr size_t kTabHeader = kTabOffBuckets + (size_t)kBuckets * kBucketWords * 8;
+// qsmd_ctx::probe_host slots the table path writes beyond the cascade's:
+// histories pass 2 took, histories per width class (grid hints)
+constexpr int kProbeTabPass2 = 10;
+constexpr int kProbeTabClass = 11;      // 3 slots
+
+struct TableArgs {
+    SearchArgs s;                 // histories, flags, max_nodes, time limit, outputs, buckets, timed_out
+    TableDev t;
+    uint32_t state0;              // the initial state (model0)
+    uint32_t* cnt;                // TCnt
+    uint32_t* class_list[3];      // n_hist entries each
+    uint32_t* heavy_list[3];
+    uint64_t budget;              // pass 1's node budget (0 = a single pass)
+    qsmd_totals* totals;          // device
+    uint32_t* probe_host;         // pinned
+};
+// bin + per class pass 1 (+ pass 2 when budget) + finish; grid1 / grid2: the
+// workgroups of each class's passes (any value >= 1 gives the same results);
+// classes: bit k set = launch class k
+hipError_t launch_table(const TableArgs& p, const uint32_t grid1[3], const uint32_t grid2[3], uint32_t classes,
+                        hipStream_t s);
+// the LDS bytes of one workgroup of class k (0, 1, 2)
+size_t table_lds_bytes(const TableDev& t, int k);
+
 // Early exit: relaxed agent-scope read (a stale value only delays skipping).
 __device__ __forceinline__ bool beyond_first_fail(const SearchArgs& a, uint32_t h) {
     return a.first_fail && h > __hip_atomic_load(a.first_fail, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);

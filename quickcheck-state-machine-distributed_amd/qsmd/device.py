@@ -60,6 +60,7 @@ EXPORTS = {
     "qsmd_close": (None, [_P]),
     "qsmd_last_error": (ctypes.c_char_p, [_P]),
     "qsmd_set_time_limit_ms": (_I, [_P, _U64]),
+    "qsmd_table_set": (_I, [_P, _P]),
     "qsmd_set_stage0_grid": (_I, [_P, _U64]),
     "qsmd_set_stage0_budget": (_I, [_P, _U64]),
     "qsmd_probe_read": (_I, [_P, _P]),
@@ -151,6 +152,7 @@ class Context:
         self._h = h
         self._lib = lib
         self._check_fn = ctypes.cast(lib.qsmd_check_batch, ctypes.c_void_p).value
+        self._table = None              # the models.TableModel this context holds (set_table)
         if time_limit_ms is not None:
             lib.qsmd_set_time_limit_ms(h, int(time_limit_ms))
 
@@ -222,6 +224,23 @@ class Context:
         """qsmd_set_time_limit_ms: the safety net's wall time per search launch
         (0 disables)."""
         self._check(self._lib.qsmd_set_time_limit_ms(self._h, int(ms)), "qsmd_set_time_limit_ms")
+
+    def set_table(self, model):
+        """qsmd_table_set: make ``model`` (a models.TableModel) the context's
+        table for QSMD_MODEL_TABLE calls; a context holds one table."""
+        st = model.c_struct()
+        self._check(self._lib.qsmd_table_set(self._h, ctypes.byref(st)), "qsmd_table_set")
+        self._table = model
+
+    @property
+    def table(self):
+        """The models.TableModel set last (None: none)."""
+        return self._table
+
+    def table_pass2(self):
+        """Histories the second pass took in the most recent QSMD_MODEL_TABLE
+        call (qsmd_get_param "table_pass2_last")."""
+        return self.get_param("table_pass2_last")
 
     def set_stage0_grid(self, max_blocks):
         self._check(self._lib.qsmd_set_stage0_grid(self._h, int(max_blocks)), "qsmd_set_stage0_grid")

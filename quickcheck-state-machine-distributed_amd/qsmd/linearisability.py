@@ -5,8 +5,10 @@
 * :func:`linearisable` keeps the reference signature
   ``linearisable transition postcondition model0 history -> Bool``
   (src/Linearisability.hs:52-58).  ``transition``/``postcondition`` must be
-  the closures of a :class:`~qsmd.models.DeviceModel` (the reference's
-  Bank / TicketDispenser models); any other closure raises -- there is no CPU
+  the closures of a :class:`~qsmd.models.DeviceModel`: the reference's
+  Bank / TicketDispenser models, or a :class:`~qsmd.models.TableModel` (any
+  finite-state model, tabulated from its closures by
+  ``TableModel.from_closures``); any other closure raises -- there is no CPU
   search to fall back to.  Model exceptions propagate as in Haskell
   (:class:`~qsmd.models.ModelError` for ``Map.!``, test/Bank.hs:128).
 * :func:`linearisable_batch` is the throughput entry point.
@@ -22,7 +24,7 @@ from dataclasses import dataclass, field
 import numpy as np
 
 from . import codec, device
-from .models import BY_ID, BY_NAME, DeviceModel, EncodeError, ModelError
+from .models import BY_ID, BY_NAME, DeviceModel, EncodeError, ModelError, TableModel
 
 __all__ = ["linearisable", "linearisable_batch", "trace", "wellformed", "replay_witness",
            "CheckResult", "NotSequential", "BudgetExceeded", "wellformed_batch"]
@@ -36,9 +38,18 @@ def _device_model(transition, postcondition) -> DeviceModel:
     for m in BY_ID.values():
         if transition is m.transition and postcondition is m.postcondition:
             return m
+    # a TableModel's closures are bound methods (a new object at every
+    # attribute access, so `is` never matches): found through their __self__
+    owner = getattr(transition, "__self__", None)
+    if (isinstance(owner, TableModel) and getattr(postcondition, "__self__", None) is owner
+            and getattr(transition, "__func__", None) is TableModel.transition
+            and getattr(postcondition, "__func__", None) is TableModel.postcondition):
+        return owner
     raise NotImplementedError(
-        "no device functor for these model closures: the GPU checker supports the "
-        "reference's Bank (test/Bank.hs) and TicketDispenser (test/TicketDispenser.hs) models")
+        "no device model for these closures: pass the closures of the reference's Bank "
+        "(test/Bank.hs) or TicketDispenser (test/TicketDispenser.hs) models, or tabulate a "
+        "finite-state model with qsmd.models.TableModel.from_closures and pass its "
+        ".transition / .postcondition")
 
 
 def _as_model(model) -> DeviceModel:
@@ -82,6 +93,8 @@ def linearisable_batch(model, histories, model0=None, *, max_nodes=0, witness=Fa
     accounts0 = m.new_account_map(model0)
     packed = m.pack_model0(model0, accounts0)
     ctx = ctx or device.default_context()
+    if isinstance(m, TableModel) and ctx.table is not m:
+        ctx.set_table(m)
     status, nodes, wit, totals = ctx.check_arrays(m.model_id, batch.hdr, batch.events, packed,
                                                   flags, max_nodes, witness)
     return CheckResult(batch, status, nodes, wit, totals)
@@ -97,7 +110,8 @@ def linearisable(transition, postcondition, model0, history, *, max_nodes=0, ctx
     if st == codec.STATUS_NONLIN:
         return False
     if st == codec.STATUS_MODEL_ERROR:
-        raise ModelError("Map.!: given key is not an element in the map")
+        raise ModelError("the postcondition raises" if isinstance(m, TableModel)
+                         else "Map.!: given key is not an element in the map")
     if st == codec.STATUS_ENCODE_ERROR:
         raise EncodeError(res.batch.encode_errors.get(0, "history cannot be encoded"))
     raise BudgetExceeded(f"search stopped after {int(res.nodes[0])} nodes")
@@ -121,6 +135,8 @@ def trace(transition, model0, history, model: DeviceModel | None = None) -> str:
         for cand in BY_ID.values():
             if transition is cand.transition:
                 m = cand
+        if m is None and isinstance(getattr(transition, "__self__", None), TableModel):
+            m = transition.__self__
         if m is None:
             raise NotImplementedError("trace needs a DeviceModel to show values")
     out = []

@@ -313,6 +313,176 @@ class Bank(DeviceModel):
         return resp if isinstance(resp, str) else f"Balance {resp[1]}"
 
 
+# ---------------------------------------------------------------------------
+# Table-driven models (include/qsmd.h QSMD_MODEL_TABLE)
+# ---------------------------------------------------------------------------
+
+MODEL_TABLE = 3
+TABLE_MAX_STATES = 256
+TABLE_MAX_SYMBOLS = 32
+
+
+class TableModelStruct(ctypes.Structure):
+    """``qsmd_table_model``."""
+    _fields_ = [("n_states", ctypes.c_uint32), ("n_inv", ctypes.c_uint32),
+                ("n_resp", ctypes.c_uint32), ("init_state", ctypes.c_uint32),
+                ("on_inv", ctypes.c_void_p), ("on_resp", ctypes.c_void_p),
+                ("post", ctypes.c_void_p), ("post_err", ctypes.c_void_p)]
+
+
+class TableModel(DeviceModel):
+    """Any finite-state model as run-time tables: no device functor, no
+    recompile.  ``states``, ``invs`` and ``resps`` are lists of hashable
+    values (at most 256 / 32 / 32); a step from state ``s`` with invocation
+    ``i`` and response ``r`` (indices) is
+
+        postcondition = bit r of post[s][i]      (post_err: it raises)
+        next state    = on_resp[on_inv[s][i]][r]
+
+    ``transition`` and ``postcondition`` are the table lookups on the state
+    *values*, with the reference's signatures, so
+    ``linearisable(m.transition, m.postcondition, model0, history)`` finds
+    ``m``.  Build one from explicit tables or from closures
+    (:meth:`from_closures`)."""
+
+    name = "table"
+    model_id = MODEL_TABLE
+
+    def __init__(self, states, invs, resps, on_inv, on_resp, post, post_err=None, init_state=0):
+        import numpy as np
+        self.states, self.invs, self.resps = list(states), list(invs), list(resps)
+        ns, ni, nr = len(self.states), len(self.invs), len(self.resps)
+        if not 1 <= ns <= TABLE_MAX_STATES:
+            raise EncodeError(f"{ns} states: a table model has 1..{TABLE_MAX_STATES}")
+        if not 1 <= ni <= TABLE_MAX_SYMBOLS or not 1 <= nr <= TABLE_MAX_SYMBOLS:
+            raise EncodeError(f"{ni} invocation / {nr} response symbols: a table model has "
+                              f"1..{TABLE_MAX_SYMBOLS} of each")
+        self.state_index = {v: k for k, v in enumerate(self.states)}
+        self.inv_index = {v: k for k, v in enumerate(self.invs)}
+        self.resp_index = {v: k for k, v in enumerate(self.resps)}
+        if len(self.state_index) != ns or len(self.inv_index) != ni or len(self.resp_index) != nr:
+            raise EncodeError("states, invs and resps must each be distinct values")
+
+        def table(x, shape, dtype, what):
+            arr = np.asarray(x)
+            if arr.shape != shape or not np.issubdtype(arr.dtype, np.integer):
+                raise EncodeError(f"{what}: an integer array of shape {shape}")
+            if arr.size and (arr.min() < 0 or arr.max() > np.iinfo(dtype).max):
+                raise EncodeError(f"{what}: entry out of range")
+            return np.ascontiguousarray(arr.astype(dtype))
+
+        self.on_inv = table(on_inv, (ns, ni), np.uint8, "on_inv")
+        self.on_resp = table(on_resp, (ns, nr), np.uint8, "on_resp")
+        self.post = table(post, (ns, ni), np.uint32, "post")
+        self.post_err = None if post_err is None else table(post_err, (ns, ni), np.uint32, "post_err")
+        if self.on_inv.max() >= ns or self.on_resp.max() >= ns:
+            raise EncodeError("on_inv / on_resp: entry >= n_states")
+        if not 0 <= int(init_state) < ns:
+            raise EncodeError("init_state >= n_states")
+        self.init_state = int(init_state)
+
+    @classmethod
+    def from_closures(cls, transition, postcondition, init_model, invs, resps, raises=ModelError):
+        """Tabulate ``transition`` / ``postcondition`` (the reference's
+        closures, src/Linearisability.hs:52-58) over the states reachable
+        from ``init_model``: breadth-first, each state's successors under
+        every ``("L", inv)`` in ``invs`` order and then every ``("R", resp)``
+        in ``resps`` order, so state 0 is ``init_model`` and the numbering is
+        reproducible.  A ``postcondition`` that raises ``raises`` becomes a
+        post_err bit.  :class:`EncodeError` past 256 states or 32 symbols."""
+        invs, resps = list(invs), list(resps)
+        if len(invs) > TABLE_MAX_SYMBOLS or len(resps) > TABLE_MAX_SYMBOLS:
+            raise EncodeError(f"{len(invs)} invocation / {len(resps)} response symbols > {TABLE_MAX_SYMBOLS}")
+        states, index = [init_model], {init_model: 0}
+        on_inv, on_resp = [], []
+        k = 0
+        while k < len(states):
+            s = states[k]
+            rows = []
+            for evs in ([("L", x) for x in invs], [("R", x) for x in resps]):
+                row = []
+                for ev in evs:
+                    t = transition(s, ev)
+                    if t not in index:
+                        if len(states) >= TABLE_MAX_STATES:
+                            raise EncodeError(f"more than {TABLE_MAX_STATES} reachable states")
+                        index[t] = len(states)
+                        states.append(t)
+                    row.append(index[t])
+                rows.append(row)
+            on_inv.append(rows[0])
+            on_resp.append(rows[1])
+            k += 1
+        post = [[0] * len(invs) for _ in states]
+        err = [[0] * len(invs) for _ in states]
+        any_err = False
+        for si, s in enumerate(states):
+            for ii, inv in enumerate(invs):
+                for ri, resp in enumerate(resps):
+                    try:
+                        if postcondition(s, inv, resp):
+                            post[si][ii] |= 1 << ri
+                    except raises:
+                        err[si][ii] |= 1 << ri
+                        any_err = True
+        return cls(states, invs, resps, on_inv, on_resp, post, err if any_err else None, 0)
+
+    @property
+    def init_model(self):
+        return self.states[self.init_state]
+
+    def _state(self, m):
+        try:
+            return self.state_index[m]
+        except (KeyError, TypeError):
+            raise EncodeError(f"not a state of this table model: {m!r}") from None
+
+    # bound methods: linearisable() finds the model through their __self__
+    def transition(self, m, ev):
+        kind, x = ev
+        s = self._state(m)
+        if kind == "L":
+            return self.states[self.on_inv[s, self.encode_inv(x, None)[0]]]
+        return self.states[self.on_resp[s, self.encode_resp(x)[0]]]
+
+    def postcondition(self, m, inv, resp):
+        s, i, r = self._state(m), self.encode_inv(inv, None)[0], self.encode_resp(resp)[0]
+        if self.post_err is not None and (int(self.post_err[s, i]) >> r) & 1:
+            raise ModelError(f"postcondition raises: {self.show_model(m)}, {self.show_inv(inv)}, "
+                             f"{self.show_resp(resp)}")
+        return bool((int(self.post[s, i]) >> r) & 1)
+
+    def encode_inv(self, inv, accounts):
+        try:
+            return self.inv_index[inv], 0, 0, 0
+        except (KeyError, TypeError):
+            raise EncodeError(f"unknown invocation symbol {inv!r}") from None
+
+    def encode_resp(self, resp):
+        try:
+            return self.resp_index[resp], 0
+        except (KeyError, TypeError):
+            raise EncodeError(f"unknown response symbol {resp!r}") from None
+
+    def decode_inv(self, code, a, b, val, accounts):
+        return self.invs[code]
+
+    def decode_resp(self, code, val):
+        return self.resps[code]
+
+    def pack_model0(self, model0, accounts):
+        if model0 is None:
+            return None
+        return ctypes.c_uint32(self._state(model0))
+
+    def c_struct(self):
+        """The ``qsmd_table_model`` of this model (pointers into its arrays,
+        which live as long as the model)."""
+        return TableModelStruct(len(self.states), len(self.invs), len(self.resps), self.init_state,
+                                self.on_inv.ctypes.data, self.on_resp.ctypes.data, self.post.ctypes.data,
+                                None if self.post_err is None else self.post_err.ctypes.data)
+
+
 TICKET = TicketDispenser()
 BANK = Bank()
 

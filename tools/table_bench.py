@@ -1,0 +1,95 @@
+"""Throughput of the table-driven model (csrc/table.hip, QSMD_MODEL_TABLE).
+
+Workload: the register model (Write / Read / Cas on values 0..3) on the
+4 clients x 16 operations generator of tests/tablegen.py with p_bug 0.03:
+65,536 distinct histories tiled to 1M, device-resident, one check call at a
+time.  Per pass-1 budget ("table_budget"; `default` = the library's, 0 = a
+single pass): 5 warm-up calls, 20 timed calls (HIP events on the stream),
+the median ms per call, histories/s, nodes/s and pass 2's share of the batch.
+One JSON line per budget.
+
+    python tools/table_bench.py [--budgets default,0] [--distinct 65536] [--n 1048576]
+"""
+
+import argparse
+import json
+import os
+import random
+import statistics
+import sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+for p in ("quickcheck-state-machine-distributed_amd", "oracle", "tests"):
+    sys.path.insert(0, os.path.join(ROOT, p))
+
+import tablegen as tg  # noqa: E402
+from qsmd import codec, device  # noqa: E402
+from qsmd.models import TableModel  # noqa: E402
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--budgets", default="default,0")
+    ap.add_argument("--distinct", type=int, default=65536)
+    ap.add_argument("--n", type=int, default=1 << 20)
+    ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--calls", type=int, default=20)
+    ap.add_argument("--max-nodes", type=int, default=tg.MAX_NODES)
+    args = ap.parse_args()
+    import torch
+
+    model = tg.REGISTER
+    m = TableModel.from_closures(model["transition"], model["postcondition"], model["init"], model["invs"],
+                                 model["resps"])
+    rng = random.Random("table_bench")
+    hists = [tg.gen_history(model, rng, 4, 16, 0.03) for _ in range(args.distinct)]
+    batch = codec.encode(m, hists)
+    reps = (args.n + args.distinct - 1) // args.distinct
+    n = reps * args.distinct
+    per = len(batch.events)
+    hdr = np.tile(batch.hdr, reps)
+    hdr["ev_off"] = (hdr["ev_off"].astype(np.int64) + np.repeat(np.arange(reps, dtype=np.int64) * per,
+                                                                 args.distinct)).astype(np.uint32)
+    ev = np.tile(batch.events, reps)
+
+    dev = torch.device("cuda:0")
+    d_hdr = torch.from_numpy(hdr.view(np.uint8)).to(dev)
+    d_ev = torch.from_numpy(ev.view(np.uint8)).to(dev)
+    d_st = torch.empty(n, dtype=torch.uint8, device=dev)
+    d_nd = torch.empty(n, dtype=torch.int64, device=dev)
+    d_tot = torch.zeros(8, dtype=torch.int64, device=dev)
+    stream = torch.cuda.current_stream().cuda_stream
+    ctx = device.Context(0, time_limit_ms=60000)
+    ctx.set_table(m)
+    default = ctx.get_param("table_budget")
+    for b in args.budgets.split(","):
+        budget = default if b == "default" else int(b)
+        ctx.set_param("table_budget", budget)
+        ms = []
+        for k in range(args.warmup + args.calls):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            ctx.check_device(3, d_hdr.data_ptr(), n, d_ev.data_ptr(), len(ev), d_st.data_ptr(), d_nd.data_ptr(),
+                             None, d_tot.data_ptr(), max_nodes=args.max_nodes, stream=stream)
+            e1.record()
+            torch.cuda.synchronize()
+            if k >= args.warmup:
+                ms.append(e0.elapsed_time(e1))
+        tot = d_tot.cpu().numpy()
+        med = statistics.median(ms)
+        print(json.dumps({
+            "workload": f"register 4x16 p_bug 0.03, {args.distinct} distinct tiled to {n}, device-resident",
+            "table_budget": budget, "is_default": budget == default, "calls": args.calls,
+            "ms_per_call_median": round(med, 4), "ms_min": round(min(ms), 4), "ms_max": round(max(ms), 4),
+            "histories_per_s": round(n / med * 1e3), "nodes_per_s": round(int(tot[7]) / med * 1e3),
+            "nodes_per_call": int(tot[7]), "pass2_histories": ctx.table_pass2(),
+            "pass2_share": round(ctx.table_pass2() / n, 5),
+            "lin": int(tot[1]), "nonlin": int(tot[2]), "budget": int(tot[5]),
+            "max_nodes": args.max_nodes}), flush=True)
+    ctx.close()
+
+
+if __name__ == "__main__":
+    main()
