@@ -92,9 +92,16 @@ __device__ __forceinline__ int stage_fresh(const SearchArgs& a, bool fresh, uint
     const uint32_t off0 = __builtin_amdgcn_readfirstlane(H.ev_off);
     const bool lane_uni = small && n_ev == N0 && H.ev_off == off0 + (uint32_t)lane * N0;
     const bool packed = F != 0ull && __ballot(fresh && !lane_uni) == 0ull && N0 > 0u;
-    if (packed) stage_packed<MODEL, G>(a, N0, off0, (uint32_t)__builtin_popcountll(F), s_ev, lane);
+    // (clean: a packed group without a marker -- every generated or encoded
+    // batch -- whose lanes need none of finish_lane's marker handling)
+    bool clean = false;
+    if (packed) clean = stage_packed<MODEL, G>(a, N0, off0, (uint32_t)__builtin_popcountll(F), s_ev, lane);
     else if (small) stage_lane<MODEL, G>(a, H, s_ev, lane);
-    if (small) finish_lane<MODEL, G>(s_ev, lane, n_ev, n_pid, a.events + H.ev_off, s);
+    if (clean) {
+        if (small) finish_lane<MODEL, G, true>(s_ev, lane, n_ev, n_pid, a.events + H.ev_off, s, N0);
+    } else if (small) {
+        finish_lane<MODEL, G>(s_ev, lane, n_ev, n_pid, a.events + H.ev_off, s);
+    }
     s.ok = s.ok && enc_ok;
 
     const bool defer = enc_ok && (!small || (s.ok && !s.fits));

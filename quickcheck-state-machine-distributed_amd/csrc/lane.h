@@ -199,6 +199,22 @@ __device__ __forceinline__ uint32_t compress(uint32_t lo, int32_t val) {
     return (plain & fit) ? w : MARK_SUSP;
 }
 
+// The same word built unconditionally, with everything compress() tests
+// ORed into `susp` instead of selected on: susp stays 0 exactly while every
+// event so far is one compress() returns as its word (stage_packed decides
+// once per group, not per event).
+template <uint32_t MODEL, class G = G32>
+__device__ __forceinline__ uint32_t compress_deferred(uint32_t lo, int32_t val, uint32_t& susp) {
+    uint32_t t;
+    asm("v_bfi_b32 %0, 7, %1, %2" : "=v"(t) : "v"(lo), "v"(lo >> 4));
+    const uint32_t sh = 23u - (__builtin_amdgcn_ubfe(lo, 7u, 1u) << 4);
+    const uint32_t w = ((uint32_t)val << sh) | __builtin_amdgcn_ubfe(t, 0u, sh);
+    const uint32_t unfit = (uint32_t)(((int32_t)w >> sh) ^ val);
+    const uint32_t bad = __builtin_amdgcn_ubfe(kCodeBad<MODEL> | 0xFFFF0000u, __builtin_amdgcn_ubfe(lo, 7u, 5u), 1u);
+    susp |= (lo & 0xF8F8F878u) | bad | unfit;
+    return w;
+}
+
 // The DFS stack: LEVELS entries x 8 bits in NW VGPRs, kept as a shift
 // register -- the top entry is byte 0, a push shifts every word up by one byte
 // (v_alignbit), a pop down -- so push and pop cost one instruction per word
@@ -289,9 +305,17 @@ __device__ __forceinline__ uint32_t magic_div(uint32_t N0) { return (uint32_t)(0
 // VALU issue, not by these round trips: 8 or 16 at a time measured no
 // faster).  A power-of-two length (the common packed batch) maps block event
 // g to its history (= column) by a shift.
-template <uint32_t MODEL, class G, bool POW2>
-__device__ __forceinline__ void stage_packed_body(const SearchArgs& a, uint32_t N0, uint32_t off0, uint32_t nh,
-                                                  uint32_t (*s_ev)[C_LANES], int lane) {
+// DEFER: the words are built without the per-event validity select
+// (compress_deferred); returns the lane's suspicion bits -- 0 when every
+// event it compressed is stored as compress() would store it.
+template <uint32_t MODEL, class G, bool POW2, bool DEFER>
+__device__ __forceinline__ uint32_t stage_packed_body(const SearchArgs& a, uint32_t N0, uint32_t off0, uint32_t nh,
+                                                      uint32_t (*s_ev)[C_LANES], int lane) {
+    uint32_t susp = 0u;
+    auto word = [&](uint32_t lo, uint32_t val) {
+        if constexpr (DEFER) return compress_deferred<MODEL, G>(lo, (int32_t)val, susp);
+        else return compress<MODEL, G>(lo, (int32_t)val);
+    };
     // history of block event g: exact for g < 2^16 (g * N0 < 2^21 << 2^32)
     const uint32_t mg = POW2 ? 0u : magic_div(N0);
     const uint32_t sh = POW2 ? (uint32_t)__builtin_ctz(N0) : 0u;
@@ -344,8 +368,8 @@ __device__ __forceinline__ void stage_packed_body(const SearchArgs& a, uint32_t 
                     c1 = col_of(2u * q + 1u, e1);
                 }
                 if (!GUARD || q < nq) {
-                    s_ev[e0][c0] = compress<MODEL, G>(x[u].x, (int32_t)x[u].y);
-                    s_ev[e1][c1] = compress<MODEL, G>(x[u].z, (int32_t)x[u].w);
+                    s_ev[e0][c0] = word(x[u].x, x[u].y);
+                    s_ev[e1][c1] = word(x[u].z, x[u].w);
                 }
             }
         };
@@ -367,22 +391,34 @@ __device__ __forceinline__ void stage_packed_body(const SearchArgs& a, uint32_t 
                 const uint32_t g = k0 + u * 64u + (uint32_t)lane;
                 uint32_t e;
                 const uint32_t c = col_of(g, e);
-                if (!GUARD || g < total_ev) s_ev[e][c] = compress<MODEL, G>(x[u].x, (int32_t)x[u].y);
+                if (!GUARD || g < total_ev) s_ev[e][c] = word(x[u].x, x[u].y);
             }
         };
         uint32_t k0 = 0;
         for (; k0 + 2u * U * 64u <= total_ev; k0 += 2u * U * 64u) step(k0, std::false_type{});
         if (k0 < total_ev) step(k0, std::true_type{});
     }
+    return susp;
 }
 
 // nh histories packed back to back with one common length N0 from event
-// off0, history hh to column hh
+// off0, history hh to column hh.  Returns true when the group is known
+// clean: every event stored as its compressed word, no marker.  The words
+// are first built without the per-event validity select, each lane ORing
+// what compress() tests into one accumulator; one ballot per group decides,
+// and a group in which any lane met an event compress() would have marked is
+// staged again with the markers (injected inputs; never a generated or
+// encoded batch).
 template <uint32_t MODEL, class G = G32>
-__device__ __forceinline__ void stage_packed(const SearchArgs& a, uint32_t N0, uint32_t off0, uint32_t nh,
+__device__ __forceinline__ bool stage_packed(const SearchArgs& a, uint32_t N0, uint32_t off0, uint32_t nh,
                                              uint32_t (*s_ev)[C_LANES], int lane) {
-    if ((N0 & (N0 - 1u)) == 0u && N0 >= 2u) stage_packed_body<MODEL, G, true>(a, N0, off0, nh, s_ev, lane);
-    else stage_packed_body<MODEL, G, false>(a, N0, off0, nh, s_ev, lane);
+    const bool pow2 = (N0 & (N0 - 1u)) == 0u && N0 >= 2u;
+    const uint32_t susp = pow2 ? stage_packed_body<MODEL, G, true, true>(a, N0, off0, nh, s_ev, lane)
+                               : stage_packed_body<MODEL, G, false, true>(a, N0, off0, nh, s_ev, lane);
+    if (__ballot(susp != 0u) == 0ull) return true;
+    if (pow2) stage_packed_body<MODEL, G, true, false>(a, N0, off0, nh, s_ev, lane);
+    else stage_packed_body<MODEL, G, false, false>(a, N0, off0, nh, s_ev, lane);
+    return false;
 }
 
 // Per lane, over its own column (evp: its raw events, read only for a
@@ -393,18 +429,23 @@ __device__ __forceinline__ void stage_packed(const SearchArgs& a, uint32_t N0, u
 // (pid masks), which costs less per DFS step than pairing the invocations
 // at staging costs per event (A/B in flight, config 2: 6.44e9 vs 6.10e9
 // histories/s).  Words beyond n_ev (stale) are masked out by ALL.
-template <uint32_t MODEL, class G = G32>
+// CLEAN (a group stage_packed found clean, every calling lane's n_ev the
+// wave-uniform n_uni): no markers can be there, so the marker plane, BAD and
+// WIDE are left out, and the pid range is one bit-sliced compare.
+template <uint32_t MODEL, class G = G32, bool CLEAN = false>
 __device__ __forceinline__ void finish_lane(uint32_t (*s_ev)[C_LANES], int lane, uint32_t n_ev, uint32_t n_pid,
-                                            const uint2* evp, StagedT<typename G::M>& s) {
+                                            const uint2* evp, StagedT<typename G::M>& s, uint32_t n_uni = 0u) {
     using M = typename G::M;
     constexpr uint32_t U = 8;
     // a ballot max: the callers may be a subset of the wavefront
-    const uint32_t n_cl = min(n_ev, (uint32_t)G::EV);
-    uint32_t n_max = 0;
+    uint32_t n_max = CLEAN ? n_uni : 0u;
+    if constexpr (!CLEAN) {
+        const uint32_t n_cl = min(n_ev, (uint32_t)G::EV);
 #pragma unroll
-    for (int b = 6; b >= 0; --b) {
-        const uint32_t t = n_max | (1u << b);
-        n_max = __ballot(n_cl >= t) ? t : n_max;
+        for (int b = 6; b >= 0; --b) {
+            const uint32_t t = n_max | (1u << b);
+            n_max = __ballot(n_cl >= t) ? t : n_max;
+        }
     }
     const M ALL = mask_below(n_ev, (M)0);
     // Per 8 events: their low nibbles (pid bits 0-2, resp bit 3) packed 4
@@ -433,19 +474,21 @@ __device__ __forceinline__ void finish_lane(uint32_t (*s_ev)[C_LANES], int lane,
         const uint32_t nib = (x0 & 0x0F0F0F0Fu) | ((x1 & 0x0F0F0F0Fu) << 4);    // event k at bits 4k..4k+3
         // marker bytes (bits 5, 6 set, 3 clear) at bit 6 of each byte, then
         // one bit per event: m has events 0, 1 at bits 0, 1, 2, 3 at 8, 9, ...
-        const uint32_t y0 = x0 & (x0 << 1) & ~(x0 << 3) & 0x40404040u;
-        const uint32_t y1 = x1 & (x1 << 1) & ~(x1 << 3) & 0x40404040u;
-        const uint32_t m = (y0 >> 6) | (y1 >> 5);
-        const uint32_t z = m | (m >> 6);                                         // events 0-3 at 0-3, 4-7 at 16-19
-        const uint32_t mk = (z & 0xFu) | ((z >> 12) & 0xF0u);
+        if constexpr (!CLEAN) {
+            const uint32_t y0 = x0 & (x0 << 1) & ~(x0 << 3) & 0x40404040u;
+            const uint32_t y1 = x1 & (x1 << 1) & ~(x1 << 3) & 0x40404040u;
+            const uint32_t m = (y0 >> 6) | (y1 >> 5);
+            const uint32_t z = m | (m >> 6);                                     // events 0-3 at 0-3, 4-7 at 16-19
+            const uint32_t mk = (z & 0xFu) | ((z >> 12) & 0xF0u);
+            MK |= (M)mk << c0;
+        }
         RESP |= (M)plane8(nib, 3) << c0;
         P0 |= (M)plane8(nib, 0) << c0;
         P1 |= (M)plane8(nib, 1) << c0;
         P2 |= (M)plane8(nib, 2) << c0;
-        MK |= (M)mk << c0;
     }
     M BAD = 0, WIDE = 0;
-    if (__ballot((MK & ALL) != (M)0)) {
+    if (!CLEAN && __ballot((MK & ALL) != (M)0)) {
 #pragma unroll 1
         for (uint32_t e = 0; e < n_max; ++e) {
             uint32_t mkw = s_ev[e][lane] & 0xF8u;
@@ -461,10 +504,20 @@ __device__ __forceinline__ void finish_lane(uint32_t (*s_ev)[C_LANES], int lane,
     P2 &= ALL;
     // events whose pid is >= n_pid (pid q's events from the bit slices)
     M GEP = 0;
+    if constexpr (CLEAN) {
+        // pid >= n_pid, most significant slice first: above in this slice, or
+        // equal in it and not below in the rest (n_pid >= 8: no 3-bit pid is)
+        const M n0 = (M)0 - (M)(n_pid & 1u), n1 = (M)0 - (M)((n_pid >> 1) & 1u), n2 = (M)0 - (M)((n_pid >> 2) & 1u);
+        const M ge0 = P0 | ~n0;
+        const M ge1 = (P1 & ~n1) | (~(P1 ^ n1) & ge0);
+        const M ge2 = (P2 & ~n2) | (~(P2 ^ n2) & ge1);
+        GEP = n_pid >= 8u ? (M)0 : ge2 & ALL;
+    } else {
 #pragma unroll
-    for (uint32_t q = 0; q < 8u; ++q) {
-        const M pq = ((q & 1u) ? P0 : ~P0) & ((q & 2u) ? P1 : ~P1) & ((q & 4u) ? P2 : ~P2) & ALL;
-        GEP |= q >= n_pid ? pq : (M)0;
+        for (uint32_t q = 0; q < 8u; ++q) {
+            const M pq = ((q & 1u) ? P0 : ~P0) & ((q & 2u) ? P1 : ~P1) & ((q & 4u) ? P2 : ~P2) & ALL;
+            GEP |= q >= n_pid ? pq : (M)0;
+        }
     }
     s.INV = ALL & ~RESP;
     s.RESP = RESP;

@@ -1,6 +1,8 @@
 """Instruction counts of the loops of one kernel (static ISA), to compare
 builds of the DFS step:  python tools/isa_loops.py csrc/compact.hip compact_searchILj2ELb0ENS_12_GLOBAL__N_13G32
-Prints each back-edge range with its VALU / SALU / LDS / v_mov counts."""
+Prints each back-edge range with its VALU / SALU / LDS / v_mov counts.
+Optional: the shortest loop to print (instructions, default 150), then
+further compiler flags."""
 
 import re
 import subprocess
@@ -8,8 +10,9 @@ import sys
 
 src, sym = sys.argv[1], sys.argv[2]
 min_len = int(sys.argv[3]) if len(sys.argv) > 3 else 150
+flags = sys.argv[4:]          # further compiler flags (-D... of an A/B build)
 asm = subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-I../include", "-Icsrc",
-                      "-S", "--cuda-device-only", src, "-o", "-"], capture_output=True, text=True).stdout
+                      *flags, "-S", "--cuda-device-only", src, "-o", "-"], capture_output=True, text=True).stdout
 lines = asm.split("\n")
 start = next(i for i, l in enumerate(lines) if l.startswith("_Z") and sym in l and l.endswith(":") is False or
              (l.startswith("_Z") and sym in l))
