@@ -140,6 +140,25 @@ typedef struct qsmd_bank_model {
  * the second, 64 to a wavefront, so a few long searches do not each hold 63
  * idle lanes.  0 = a single pass.  Results are unchanged.  qsmd_get_param
  * "table_pass2_last": histories the second pass took in the most recent
+ * table call (waits for it).
+ * Knob "table_memo" (default 0 = off: exactly the launches above; else a
+ * power of two in 2..2^20, anything else QSMD_ERR_ARG): the second pass keeps
+ * an exact-count state memo of that many entries per lane slot.  The subtree
+ * below a node depends only on (remaining events, state); a subtree the
+ * search backtracks out of is recorded under that full key with the nodes it
+ * counted, and a later descent into the same key counts them at once and
+ * backtracks.  Status, node count and witness stay the reference's; when
+ * max_nodes (or 2^64 - 1 with max_nodes 0) falls inside a recorded subtree
+ * the result is QSMD_STATUS_BUDGET with nodes == that limit.  A tree of 1e18
+ * nodes with a few hundred distinct states is decided in a few thousand
+ * iterations.  Limits: the memo serves the second pass only, so with
+ * "table_budget" 0 there is none; it is opt-in; the tables (pass 2's
+ * workgroups x 64 x entries x 32 bytes, device memory, allocated on first
+ * use, kept until qsmd_close; QSMD_ERR_NOMEM when that fails) are held to
+ * 1 GiB by launching fewer workgroups -- one workgroup's tables are always
+ * allowed, 2 GiB at 2^20 entries.  Diagnostic knob "table_memo_grid": 0 =
+ * automatic, else pass 2's workgroups at most while the memo is on.
+ * qsmd_get_param "table_memo_hits_last": the memo's hits in the most recent
  * table call (waits for it).  The cascade's knobs, qsmd_probe_read and the
  * timing ring (qsmd_last_kernel_ms, qsmd_timing_read) do not apply to table
  * calls. */

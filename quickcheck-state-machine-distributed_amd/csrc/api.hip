@@ -172,6 +172,13 @@ struct qsmd_ctx {
     uint64_t table_budget = 256;
     char* tws = nullptr;
     size_t tws_bytes = 0;
+    // pass 2's state memo ("table_memo", entries per lane slot; 0 = off): one
+    // table per lane slot of pass 2's grid, entries tagged by call epoch
+    uint64_t table_memo = 0;
+    uint64_t table_memo_grid = 0;      // diagnostic: pass 2's workgroups at most (0 = automatic)
+    char* tm = nullptr;
+    size_t tm_bytes = 0;
+    uint32_t tm_epoch = 0;
     uint8_t* wf_rank_host = nullptr;   // wellformed: pid rank table (pinned) and its device copy
     char* wf_rank_dev = nullptr;
     size_t wf_rank_bytes = 0;
@@ -382,6 +389,7 @@ void qsmd_close(qsmd_ctx* c) {
     if (c->sx) (void)hipFree(c->sx);
     if (c->tab_blob) (void)hipFree(c->tab_blob);
     if (c->tws) (void)hipFree(c->tws);
+    if (c->tm) (void)hipFree(c->tm);
     if (c->mt) (void)hipFree(c->mt);
     if (c->rs) (void)hipFree(c->rs);
     if (c->xm) (void)hipFree(c->xm);
@@ -498,6 +506,13 @@ int qsmd_set_param(qsmd_ctx* c, const char* name, uint64_t value) {
         c->fold = value;
     } else if (n == "table_budget") {       // QSMD_MODEL_TABLE: pass 1's node budget (0 = a single pass)
         c->table_budget = value;
+    } else if (n == "table_memo") {         // pass 2's state memo: entries per lane slot (0 = off)
+        if (value && (value < 2 || value > (1ull << 20) || (value & (value - 1))))
+            return fail(c, QSMD_ERR_ARG, "table_memo: 0 (off) or a power of two in 2..2^20");
+        c->table_memo = value;
+    } else if (n == "table_memo_grid") {    // diagnostic: pass 2's workgroups at most with the memo (0 = automatic)
+        if (value > 65536) return fail(c, QSMD_ERR_ARG, "table_memo_grid in 0..65536");
+        c->table_memo_grid = value;
     } else if (n == "heavy_mode") {
         if (value > 2) return fail(c, QSMD_ERR_ARG, "heavy_mode: 0 = wave, 1 = lane, 2 = auto");
         c->heavy_mode = value;
@@ -774,6 +789,42 @@ static int check_table_locked(qsmd_ctx* c, const qsmd_hdr* hdr, uint64_t n_hist,
     for (int k = 0; k < 3; ++k) {
         grid1[k] = (uint32_t)std::min<uint64_t>(groups, cap1);
         grid2[k] = (uint32_t)g2;
+    }
+    // pass 2's state memo: one table of table_memo entries (32 B each) per
+    // lane slot of pass 2's grid, at most 1 GiB (a smaller grid; one
+    // workgroup's tables are always allowed: 2 GiB at 2^20 entries).
+    // Entries are tagged by call epoch: cleared when allocated and when the
+    // 24-bit epochs wrap, not per call.
+    if (c->table_memo && c->table_budget) {
+        const uint64_t per_wg = 64ull * c->table_memo * 32ull;
+        uint64_t gm = std::max<uint64_t>((1ull << 30) / per_wg, 1);
+        if (c->table_memo_grid) gm = std::min<uint64_t>(gm, c->table_memo_grid);
+        gm = std::min<uint64_t>(gm, g2);
+        const size_t need = (size_t)(gm * per_wg);
+        if (c->tm_bytes < need) {
+            if (c->tm) {
+                quiesce(c);
+                (void)hipFree(c->tm);
+                c->tm = nullptr;
+                c->tm_bytes = 0;
+            }
+            const hipError_t e = hipMalloc(reinterpret_cast<void**>(&c->tm), need);
+            if (e != hipSuccess) {
+                (void)hipGetLastError();
+                c->tm = nullptr;
+                return fail(c, QSMD_ERR_NOMEM, "hipMalloc table memo", e);
+            }
+            c->tm_bytes = need;
+            HIP_TRY(c, hipMemsetAsync(c->tm, 0, c->tm_bytes, s), "memset table memo");
+        }
+        if (((++c->tm_epoch) & 0xFFFFFFu) == 0u) {   // 24-bit tags wrapped: clear
+            HIP_TRY(c, hipMemsetAsync(c->tm, 0, c->tm_bytes, s), "memset table memo");
+            ++c->tm_epoch;
+        }
+        p.memo = reinterpret_cast<uint4*>(c->tm);
+        p.memo_entries = (uint32_t)c->table_memo;
+        p.memo_epoch = c->tm_epoch & 0xFFFFFFu;
+        for (int k = 0; k < 3; ++k) grid2[k] = (uint32_t)gm;
     }
     HIP_TRY(c, launch_table(p, grid1, grid2, (route & kClassesKnown) ? (route & 7u) : 7u, s), "table launch");
     const bool own = s == c->stream;
@@ -1430,6 +1481,13 @@ int qsmd_get_param(qsmd_ctx* c, const char* name, uint64_t* out) {
     } else if (n == "table_pass2_last") {    // histories pass 2 took in the most recent QSMD_MODEL_TABLE call
         quiesce(c);
         *out = c->probe_host[kProbeTabPass2];
+    } else if (n == "table_memo") {
+        *out = c->table_memo;
+    } else if (n == "table_memo_grid") {
+        *out = c->table_memo_grid;
+    } else if (n == "table_memo_hits_last") {   // memo hits of the most recent QSMD_MODEL_TABLE call
+        quiesce(c);
+        *out = c->probe_host[kProbeTabHits] | ((uint64_t)c->probe_host[kProbeTabHits + 1] << 32);
     } else {
         return fail(c, QSMD_ERR_ARG, "unknown parameter");
     }

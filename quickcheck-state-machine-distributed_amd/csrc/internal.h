@@ -395,6 +395,7 @@ enum TCnt : uint32_t {
     TC_CLASS = 0,       // histories per width class (32 / 64 / 128 events): 3 counters
     TC_HEAVY = 3,       // histories over the pass-1 budget, per class: 3 counters
     TC_TIMED = 6,       // the time limit fired
+    TC_HITS = 8,        // pass 2's memo hits: one u64 (two counters, 8-byte aligned)
     TC_N = 16
 };
 constexpr size_t kTabOffBuckets = 256;
@@ -403,6 +404,7 @@ constexpr size_t kTabHeader = kTabOffBuckets + (size_t)kBuckets * kBucketWords *
 // histories pass 2 took, histories per width class (grid hints)
 constexpr int kProbeTabPass2 = 10;
 constexpr int kProbeTabClass = 11;      // 3 slots
+constexpr int kProbeTabHits = 14;       // 2 slots: pass 2's memo hits, lo / hi
 
 struct TableArgs {
     SearchArgs s;                 // histories, flags, max_nodes, time limit, outputs, buckets, timed_out
@@ -414,6 +416,10 @@ struct TableArgs {
     uint64_t budget;              // pass 1's node budget (0 = a single pass)
     qsmd_totals* totals;          // device
     uint32_t* probe_host;         // pinned
+    uint4* memo;                  // pass 2's state memo ("table_memo"): grid2 x 64 tables of memo_entries
+                                  // entries of 2 x uint4, or null (off: today's launches)
+    uint32_t memo_entries;        // a power of two
+    uint32_t memo_epoch;          // this call's tag (24 bits)
 };
 // bin + per class pass 1 (+ pass 2 when budget) + finish; grid1 / grid2: the
 // workgroups of each class's passes (any value >= 1 gives the same results);
@@ -421,7 +427,8 @@ struct TableArgs {
 hipError_t launch_table(const TableArgs& p, const uint32_t grid1[3], const uint32_t grid2[3], uint32_t classes,
                         hipStream_t s);
 // the LDS bytes of one workgroup of class k (0, 1, 2)
-size_t table_lds_bytes(const TableDev& t, int k);
+// (memo: pass 2 with the state memo, + 8 B per level and lane)
+size_t table_lds_bytes(const TableDev& t, int k, bool memo = false);
 
 // Early exit: relaxed agent-scope read (a stale value only delays skipping).
 __device__ __forceinline__ bool beyond_first_fail(const SearchArgs& a, uint32_t h) {

@@ -33,7 +33,9 @@
 // class runs two passes: pass 1 with a node budget ("table_budget"), a search
 // over it appended to the class's heavy list; pass 2 grid-stride over that
 // list (count read on the device), each history searched again from the root
-// -- so the node counts stay the reference's.
+// -- so the node counts stay the reference's.  With the knob "table_memo"
+// pass 2 runs the MEMO instantiation: an exact-count state memo per lane slot
+// (TableMemo below; the counts, the verdict and the witness are unchanged).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -90,6 +92,67 @@ struct TabLds {
     const uint8_t* on_resp;
 };
 
+__device__ __forceinline__ void to_words(uint32_t m, uint32_t* w) { w[0] = m; }
+__device__ __forceinline__ void to_words(uint64_t m, uint32_t* w) { w[0] = (uint32_t)m; w[1] = (uint32_t)(m >> 32); }
+__device__ __forceinline__ void to_words(const M128& m, uint32_t* w) {
+    w[0] = (uint32_t)m.lo; w[1] = (uint32_t)(m.lo >> 32); w[2] = (uint32_t)m.hi; w[3] = (uint32_t)(m.hi >> 32);
+}
+
+// The exact-count state memo of pass 2 (knob "table_memo").
+// By Lemma L1 the subtree below a node depends only on (rem, state), and a
+// subtree the search backtracks out of has failed after counting a fixed
+// number of nodes.  One lane's view: its private direct-mapped table in HBM
+// (32 B per entry: count lo | count hi | epoch << 8 | state | history index,
+// then the rem words, zero-padded to four), its LDS column of node counts at
+// entry per level, and a 64-bit map of the slots (mod 64) it has written for
+// this history, which gates the HBM probe.
+template <class M>
+struct TableMemo {
+    static constexpr int NW = TW<M>::NW;
+    uint4* tab;             // the lane's table
+    uint64_t* entry;        // LDS: [level][lane], this lane's column
+    uint32_t mask;          // entries - 1
+    uint32_t tag;           // epoch << 8
+    uint32_t h;
+    uint32_t hits;
+    uint64_t wr;
+    bool skip;              // the node being left was a hit: recorded already
+
+    __device__ __forceinline__ uint32_t slot_of(const uint32_t* w, uint32_t state) const {
+        constexpr uint32_t K[4] = {0x9E3779B1u, 0x85EBCA77u, 0xC2B2AE3Du, 0x27D4EB2Fu};
+        uint32_t x = state * 0x165667B1u;
+#pragma unroll
+        for (int k = 0; k < NW; ++k) x ^= w[k] * K[k];
+        x ^= x >> 16;
+        x *= 0x85EBCA6Bu;
+        x ^= x >> 13;
+        return x & mask;
+    }
+    __device__ __forceinline__ void begin(uint32_t hist) {
+        h = hist;
+        wr = 0ull;
+        skip = false;
+    }
+    __device__ __forceinline__ void record(const M& rem, uint32_t state, uint64_t count) {
+        uint32_t w[4] = {0u, 0u, 0u, 0u};
+        to_words(rem, w);
+        const uint32_t slot = slot_of(w, state);
+        tab[2u * slot] = make_uint4((uint32_t)count, (uint32_t)(count >> 32), tag | state, h);
+        tab[2u * slot + 1u] = make_uint4(w[0], w[1], w[2], w[3]);
+        wr |= 1ull << (slot & 63u);
+    }
+    // the whole key is compared: epoch, state, history, every rem word
+    __device__ __forceinline__ bool probe(const M& rem, uint32_t state, uint64_t& count) const {
+        uint32_t w[4] = {0u, 0u, 0u, 0u};
+        to_words(rem, w);
+        const uint32_t slot = slot_of(w, state);
+        if (!((wr >> (slot & 63u)) & 1ull)) return false;
+        const uint4 a = tab[2u * slot], b = tab[2u * slot + 1u];
+        count = a.x | ((uint64_t)a.y << 32);
+        return a.z == (tag | state) && a.w == h && b.x == w[0] && b.y == w[1] && b.z == w[2] && b.w == w[3];
+    }
+};
+
 // One lane's search state (registers) over its LDS columns.
 template <class M>
 struct TableDFS {
@@ -127,8 +190,12 @@ struct TableDFS {
     // candidate.  -1 = go on, kTerm = the search ended (finish()), or
     // QSMD_STATUS_BUDGET (limit nodes counted; nothing moved) /
     // QSMD_STATUS_MODEL_ERROR.
+    // MEMO (pass 2 with "table_memo"): a subtree left by a backtrack is
+    // recorded with the nodes it counted, a descent into a recorded state
+    // counts them and backtracks at once (the rule of memo.hip's memo_step).
+    template <bool MEMO>
     __device__ __forceinline__ int step(const TableDev& t, const TabLds& L, const uint16_t* ev, uint16_t* stk,
-                                        int lane, uint64_t limit) {
+                                        int lane, uint64_t limit, TableMemo<M>& mm) {
         const bool empty = !MO::any(cand);
         // no children: a leaf => True (any' []), the root => False (any [])
         if (empty && (found == 0u || depth == 0u)) return kTerm;
@@ -136,6 +203,11 @@ struct TableDFS {
             // backtrack: the parent's remaining set by Lemma L1, its state
             // from the stack
             --depth;
+            if constexpr (MEMO) {
+                // (rem, state) are still the node's being left
+                if (!mm.skip) mm.record(rem, state, nodes - mm.entry[depth * C_LANES]);
+                mm.skip = false;
+            }
             const uint32_t st = stk[col16(depth, lane)];
             const uint32_t j = st & 0xFFu;
             state = st >> 8;
@@ -167,6 +239,22 @@ struct TableDFS {
             rem = rem & ~(MO::lowest(rem & pmj & INV) | MO::bit((int)r));
             cand = t_cands(rem, INV, RESP);
             found = 0u;
+            if constexpr (MEMO) {
+                mm.entry[(depth - 1u) * C_LANES] = nodes;
+                uint64_t c;
+                if (mm.probe(rem, state, c)) {
+                    ++mm.hits;
+                    uint64_t sum;
+                    if (__builtin_add_overflow(nodes, c, &sum) || sum > limit) {   // the budget falls inside that subtree
+                        nodes = limit;
+                        return QSMD_STATUS_BUDGET;
+                    }
+                    nodes = sum;                 // the subtree's nodes, counted; it failed
+                    cand = t_zero<M>();
+                    found = 1u;
+                    mm.skip = true;
+                }
+            }
         }
         return -1;
     }
@@ -251,7 +339,9 @@ __global__ __launch_bounds__(C_LANES) void table_bin(TableArgs a) {
 
 // PASS2 false: the class list with the pass-1 budget; true: the class's
 // heavy list, every search to its end.
-template <class M>
+// MEMO: pass 2 with the state memo (a.memo: one table of a.memo_entries
+// entries per lane slot of the grid).
+template <class M, bool MEMO>
 __global__ __launch_bounds__(C_LANES) void table_search(TableArgs a, uint32_t pass2) {
     constexpr int EV = TW<M>::EV, K = TW<M>::CLASS;
     extern __shared__ uint32_t lds[];
@@ -260,10 +350,19 @@ __global__ __launch_bounds__(C_LANES) void table_search(TableArgs a, uint32_t pa
     const uint32_t total = a.cnt[(pass2 ? TC_HEAVY : TC_CLASS) + K];
     if ((uint64_t)blockIdx.x * C_LANES >= total) return;
 
-    // LDS: events [EV / 2][64] words, stack [EV / 4][64] words, the tables
+    // LDS: events [EV / 2][64] words, stack [EV / 4][64] words, (MEMO: the
+    // node counts at entry, [EV / 2][64] u64,) the tables
     uint16_t* ev = reinterpret_cast<uint16_t*>(lds);
     uint16_t* stk = reinterpret_cast<uint16_t*>(lds + (EV / 2) * C_LANES);
-    uint32_t* tab = lds + (EV / 2 + EV / 4) * C_LANES;
+    uint32_t* tab = lds + (EV / 2 + EV / 4 + (MEMO ? EV : 0)) * C_LANES;
+    TableMemo<M> mm;
+    if constexpr (MEMO) {
+        mm.entry = reinterpret_cast<uint64_t*>(lds + (EV / 2 + EV / 4) * C_LANES) + lane;
+        mm.tab = a.memo + ((uint64_t)blockIdx.x * C_LANES + (uint64_t)lane) * (uint64_t)a.memo_entries * 2ull;
+        mm.mask = a.memo_entries - 1u;
+        mm.tag = a.memo_epoch << 8;
+        mm.hits = 0u;
+    }
     {
         const uint4* src = reinterpret_cast<const uint4*>(a.t.blob);
         uint4* dst = reinterpret_cast<uint4*>(tab);
@@ -298,11 +397,12 @@ __global__ __launch_bounds__(C_LANES) void table_search(TableArgs a, uint32_t pa
             status = stage_table<M>(a, H, ev, lane, dfs) ? -1 : QSMD_STATUS_ENCODE_ERROR;
             if (status == -1) dfs.init(a.state0);
         }
+        if constexpr (MEMO) mm.begin(h);
         // the search, the time limit checked every 1024 iterations (a
         // wavefront-uniform counter: the loop runs while any lane searches)
         while (__ballot(status == -1) != 0ull) {
             for (uint32_t k = 0; k < 1024u; ++k) {
-                if (status == -1) status = dfs.step(a.t, L, ev, stk, lane, limit);
+                if (status == -1) status = dfs.template step<MEMO>(a.t, L, ev, stk, lane, limit, mm);
                 if (__ballot(status == -1) == 0ull) break;
             }
             if (status == -1 && a.s.time_limit && __builtin_amdgcn_s_memrealtime() - t0 > a.s.time_limit) {
@@ -325,6 +425,14 @@ __global__ __launch_bounds__(C_LANES) void table_search(TableArgs a, uint32_t pa
             }
         }
         cnt.add(out, status, dfs.nodes);
+        if constexpr (MEMO) {
+            // the group's hits: one atomic per wavefront
+            const uint64_t hits = wave_sum64(mm.hits);
+            mm.hits = 0u;
+            if (lane == 0 && hits)
+                __hip_atomic_fetch_add(reinterpret_cast<unsigned long long*>(a.cnt + TC_HITS), (unsigned long long)hits,
+                                       __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
     }
     cnt.flush(a.s.buckets, lane);
 }
@@ -341,27 +449,29 @@ __global__ __launch_bounds__(C_LANES) void table_finish(TableArgs a) {
         a.probe_host[C_TIMED] = a.cnt[TC_TIMED];
         a.probe_host[kProbeTabPass2] = a.cnt[TC_HEAVY] + a.cnt[TC_HEAVY + 1] + a.cnt[TC_HEAVY + 2];
         for (int c = 0; c < 3; ++c) a.probe_host[kProbeTabClass + c] = a.cnt[TC_CLASS + c];
+        a.probe_host[kProbeTabHits] = a.cnt[TC_HITS];
+        a.probe_host[kProbeTabHits + 1] = a.cnt[TC_HITS + 1];
         __threadfence_system();
     }
 }
 
-template <class M>
+template <class M, bool MEMO>
 hipError_t launch_class(const TableArgs& p, uint32_t grid, uint32_t pass2, hipStream_t s) {
-    const size_t lds = table_lds_bytes(p.t, TW<M>::CLASS);
+    const size_t lds = table_lds_bytes(p.t, TW<M>::CLASS, MEMO);
     if (lds > 64u * 1024u) {
         static std::atomic<int> set[kAttrDevices];
-        const hipError_t e = ensure_dyn_lds(reinterpret_cast<const void*>(&table_search<M>), set, lds);
+        const hipError_t e = ensure_dyn_lds(reinterpret_cast<const void*>(&table_search<M, MEMO>), set, lds);
         if (e != hipSuccess) return e;
     }
-    hipLaunchKernelGGL((table_search<M>), dim3(grid), dim3(C_LANES), lds, s, p, pass2);
+    hipLaunchKernelGGL((table_search<M, MEMO>), dim3(grid), dim3(C_LANES), lds, s, p, pass2);
     return hipGetLastError();
 }
 
 }  // namespace
 
-size_t table_lds_bytes(const TableDev& t, int k) {
+size_t table_lds_bytes(const TableDev& t, int k, bool memo) {
     const size_t ev = k == 0 ? 32 : (k == 1 ? 64 : 128);
-    return ((ev / 2 + ev / 4) * C_LANES + (size_t)t.blob_words) * 4;
+    return ((ev / 2 + ev / 4 + (memo ? ev : 0)) * C_LANES + (size_t)t.blob_words) * 4;
 }
 
 hipError_t launch_table(const TableArgs& p, const uint32_t grid1[3], const uint32_t grid2[3], uint32_t classes,
@@ -372,9 +482,15 @@ hipError_t launch_table(const TableArgs& p, const uint32_t grid1[3], const uint3
     hipError_t e = hipGetLastError();
     for (uint32_t pass2 = 0; pass2 < (p.budget ? 2u : 1u) && e == hipSuccess; ++pass2) {
         const uint32_t* g = pass2 ? grid2 : grid1;
-        if (e == hipSuccess && (classes & 1u)) e = launch_class<uint32_t>(p, g[0], pass2, s);
-        if (e == hipSuccess && (classes & 2u)) e = launch_class<uint64_t>(p, g[1], pass2, s);
-        if (e == hipSuccess && (classes & 4u)) e = launch_class<M128>(p, g[2], pass2, s);
+        if (pass2 && p.memo) {
+            if (e == hipSuccess && (classes & 1u)) e = launch_class<uint32_t, true>(p, g[0], pass2, s);
+            if (e == hipSuccess && (classes & 2u)) e = launch_class<uint64_t, true>(p, g[1], pass2, s);
+            if (e == hipSuccess && (classes & 4u)) e = launch_class<M128, true>(p, g[2], pass2, s);
+            continue;
+        }
+        if (e == hipSuccess && (classes & 1u)) e = launch_class<uint32_t, false>(p, g[0], pass2, s);
+        if (e == hipSuccess && (classes & 2u)) e = launch_class<uint64_t, false>(p, g[1], pass2, s);
+        if (e == hipSuccess && (classes & 4u)) e = launch_class<M128, false>(p, g[2], pass2, s);
     }
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(table_finish, dim3(1), dim3(C_LANES), 0, s, p);

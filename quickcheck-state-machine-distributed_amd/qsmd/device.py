@@ -242,6 +242,12 @@ class Context:
         call (qsmd_get_param "table_pass2_last")."""
         return self.get_param("table_pass2_last")
 
+    def table_memo_hits(self):
+        """Hits of the second pass's state memo (knob "table_memo") in the
+        most recent QSMD_MODEL_TABLE call (qsmd_get_param
+        "table_memo_hits_last")."""
+        return self.get_param("table_memo_hits_last")
+
     def set_stage0_grid(self, max_blocks):
         self._check(self._lib.qsmd_set_stage0_grid(self._h, int(max_blocks)), "qsmd_set_stage0_grid")
 

@@ -86,8 +86,10 @@ class CheckResult:
 
 
 def linearisable_batch(model, histories, model0=None, *, max_nodes=0, witness=False,
-                       flags=device.QSMD_FLAG_EXHAUSTIVE, ctx=None) -> CheckResult:
-    """Check many histories in one device call."""
+                       flags=device.QSMD_FLAG_EXHAUSTIVE, ctx=None, table_memo=None) -> CheckResult:
+    """Check many histories in one device call.  ``table_memo`` (table models:
+    entries per lane slot of the second pass's state memo, 0 = off) sets the
+    context's "table_memo" knob for this call and restores it afterwards."""
     m = _as_model(model)
     batch = codec.encode(m, histories, model0)
     accounts0 = m.new_account_map(model0)
@@ -95,15 +97,24 @@ def linearisable_batch(model, histories, model0=None, *, max_nodes=0, witness=Fa
     ctx = ctx or device.default_context()
     if isinstance(m, TableModel) and ctx.table is not m:
         ctx.set_table(m)
-    status, nodes, wit, totals = ctx.check_arrays(m.model_id, batch.hdr, batch.events, packed,
-                                                  flags, max_nodes, witness)
+    saved = None
+    if table_memo is not None:
+        saved = ctx.get_param("table_memo")
+        ctx.set_param("table_memo", table_memo)
+    try:
+        status, nodes, wit, totals = ctx.check_arrays(m.model_id, batch.hdr, batch.events, packed,
+                                                      flags, max_nodes, witness)
+    finally:
+        if saved is not None:
+            ctx.set_param("table_memo", saved)
     return CheckResult(batch, status, nodes, wit, totals)
 
 
-def linearisable(transition, postcondition, model0, history, *, max_nodes=0, ctx=None) -> bool:
-    """``linearisable`` (src/Linearisability.hs:52-69) on the GPU."""
+def linearisable(transition, postcondition, model0, history, *, max_nodes=0, ctx=None, table_memo=None) -> bool:
+    """``linearisable`` (src/Linearisability.hs:52-69) on the GPU
+    (``table_memo``: see :func:`linearisable_batch`)."""
     m = _device_model(transition, postcondition)
-    res = linearisable_batch(m, [history], model0, max_nodes=max_nodes, ctx=ctx)
+    res = linearisable_batch(m, [history], model0, max_nodes=max_nodes, ctx=ctx, table_memo=table_memo)
     st = int(res.status[0])
     if st == codec.STATUS_LIN:
         return True

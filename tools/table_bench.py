@@ -6,9 +6,11 @@ Workload: the register model (Write / Read / Cas on values 0..3) on the
 time.  Per pass-1 budget ("table_budget"; `default` = the library's, 0 = a
 single pass): 5 warm-up calls, 20 timed calls (HIP events on the stream),
 the median ms per call, histories/s, nodes/s and pass 2's share of the batch.
-One JSON line per budget.
+One JSON line per budget and memo size ("table_memo", --memo: entries per
+lane slot of pass 2's state memo, 0 = off), the sizes crossed with every
+budget.  --rounds R repeats the whole cross R times (interleaved).
 
-    python tools/table_bench.py [--budgets default,0] [--distinct 65536] [--n 1048576]
+    python tools/table_bench.py [--budgets default,0] [--memo 0,64,256,1024,4096] [--distinct 65536] [--n 1048576]
 """
 
 import argparse
@@ -32,6 +34,8 @@ from qsmd.models import TableModel  # noqa: E402
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--budgets", default="default,0")
+    ap.add_argument("--memo", default="0")
+    ap.add_argument("--rounds", type=int, default=1)
     ap.add_argument("--distinct", type=int, default=65536)
     ap.add_argument("--n", type=int, default=1 << 20)
     ap.add_argument("--warmup", type=int, default=5)
@@ -64,9 +68,11 @@ def main():
     ctx = device.Context(0, time_limit_ms=60000)
     ctx.set_table(m)
     default = ctx.get_param("table_budget")
-    for b in args.budgets.split(","):
+    cross = [(b, int(e)) for _ in range(args.rounds) for b in args.budgets.split(",") for e in args.memo.split(",")]
+    for b, entries in cross:
         budget = default if b == "default" else int(b)
         ctx.set_param("table_budget", budget)
+        ctx.set_param("table_memo", entries)
         ms = []
         for k in range(args.warmup + args.calls):
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -81,7 +87,8 @@ def main():
         med = statistics.median(ms)
         print(json.dumps({
             "workload": f"register 4x16 p_bug 0.03, {args.distinct} distinct tiled to {n}, device-resident",
-            "table_budget": budget, "is_default": budget == default, "calls": args.calls,
+            "table_budget": budget, "is_default": budget == default, "table_memo": entries,
+            "table_memo_hits": ctx.table_memo_hits(), "calls": args.calls,
             "ms_per_call_median": round(med, 4), "ms_min": round(min(ms), 4), "ms_max": round(max(ms), 4),
             "histories_per_s": round(n / med * 1e3), "nodes_per_s": round(int(tot[7]) / med * 1e3),
             "nodes_per_call": int(tot[7]), "pass2_histories": ctx.table_pass2(),
