@@ -175,6 +175,42 @@ typedef struct qsmd_table_model {
                                   raises -> QSMD_STATUS_MODEL_ERROR (wins over post) */
 } qsmd_table_model;
 
+/* Wide table-driven model: QSMD_MODEL_TABLE's semantics and call surface for
+ * a model beyond its limits -- up to 65,536 states (16 bits) and 256
+ * invocation / 256 response symbols (the event's `code` byte).  The tables
+ * stay in device memory instead of LDS, so a step pays two dependent
+ * device-memory reads where model 3 pays LDS reads: a model that fits model 3
+ * should use model 3 (DESIGN.md §10c has the measured ratio).
+ *   - on_inv [n_states][n_inv] and on_resp [n_states][n_resp] are uint16_t;
+ *   - post and the optional post_err are [n_states][n_inv][post_words] with
+ *     post_words = ceil(n_resp / 32); response r is bit r & 31 of word r >> 5;
+ *   - a step is model 3's: post, post_err wins, next state
+ *     on_resp[on_inv[s][i]][r].
+ * QSMD_WTABLE_MAX_BYTES caps the context's device copy (n_states * n_inv *
+ * (1 + post_words * (post_err ? 2 : 1)) * 4 bytes for on_inv and the
+ * postcondition words, plus n_states * n_resp * 2 for on_resp, rounded up to
+ * 16).  64 MiB is a design decision, not a measurement: a quarter of the
+ * 256 MiB Infinity Cache, so the tables and the state memo stay cached
+ * together.
+ * qsmd_check_batch / qsmd_check_batch_device with QSMD_MODEL_WTABLE behave as
+ * documented for QSMD_MODEL_TABLE above, with hdr.model_id 4, the wide
+ * table's n_states / n_inv / n_resp, and qsmd_wtable_set in place of
+ * qsmd_table_set.  The knobs "table_budget", "table_memo", "table_memo_grid"
+ * and the read-outs "table_pass2_last", "table_memo_hits_last" apply
+ * unchanged.  A context holds one narrow and one wide table, independently. */
+#define QSMD_MODEL_WTABLE 4u
+#define QSMD_WTABLE_MAX_STATES 65536
+#define QSMD_WTABLE_MAX_INV      256
+#define QSMD_WTABLE_MAX_RESP     256
+#define QSMD_WTABLE_MAX_BYTES (64u << 20)
+typedef struct qsmd_wtable_model {
+    uint32_t n_states, n_inv, n_resp, init_state;
+    const uint16_t* on_inv;    /* [n_states][n_inv]  transition m (Left inv)   */
+    const uint16_t* on_resp;   /* [n_states][n_resp] transition m (Right resp) */
+    const uint32_t* post;      /* [n_states][n_inv][post_words]                */
+    const uint32_t* post_err;  /* same shape, may be NULL (wins over post)     */
+} qsmd_wtable_model;
+
 /* -------------------------------------------------------------- results */
 
 #define QSMD_STATUS_NONLINEARISABLE 0u  /* linearisable ... == False        */
@@ -236,6 +272,14 @@ uint32_t qsmd_abi_version(void);
  * otherwise QSMD_ERR_ARG, and the context keeps its previous table.  Waits
  * for the context's last call. */
 int qsmd_table_set(qsmd_ctx* ctx, const qsmd_table_model* model);
+
+/* Set the context's wide table model (QSMD_MODEL_WTABLE; one per context,
+ * beside the narrow one).  The rules of qsmd_table_set: dimensions, every
+ * on_inv / on_resp entry, init_state, the non-NULL tables and
+ * QSMD_WTABLE_MAX_BYTES are checked -- otherwise QSMD_ERR_ARG, and the
+ * context keeps its previous wide table.  Waits for the context's last call;
+ * the device copy is freed in qsmd_close. */
+int qsmd_wtable_set(qsmd_ctx* ctx, const qsmd_wtable_model* model);
 
 /* Threading and streams.  Every entry point of one context serialises on the
  * context's mutex, and the check calls of one context are ordered: a call on

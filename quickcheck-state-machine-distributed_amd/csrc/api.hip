@@ -18,6 +18,7 @@
 #include <unistd.h>
 #include <mutex>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "internal.h"
@@ -179,6 +180,16 @@ struct qsmd_ctx {
     char* tm = nullptr;
     size_t tm_bytes = 0;
     uint32_t tm_epoch = 0;
+    // QSMD_MODEL_WTABLE (csrc/wtable.hip): the wide table set by
+    // qsmd_wtable_set, beside the narrow one.  Its calls use the narrow
+    // path's workspace, knobs and memo tables; the two paths tag a memo entry
+    // differently (epoch 24 | state 8 against 16 | 16), so the tables are
+    // cleared when the path that wrote them last is not the one about to run
+    uint32_t* wtab_blob = nullptr;
+    WTableDev wtab{};
+    uint32_t wtab_init = 0;
+    bool tm_wide = false;
+    uint32_t tm_epoch_w = 0;
     uint8_t* wf_rank_host = nullptr;   // wellformed: pid rank table (pinned) and its device copy
     char* wf_rank_dev = nullptr;
     size_t wf_rank_bytes = 0;
@@ -388,6 +399,7 @@ void qsmd_close(qsmd_ctx* c) {
     if (c->ws) (void)hipFree(c->ws);
     if (c->sx) (void)hipFree(c->sx);
     if (c->tab_blob) (void)hipFree(c->tab_blob);
+    if (c->wtab_blob) (void)hipFree(c->wtab_blob);
     if (c->tws) (void)hipFree(c->tws);
     if (c->tm) (void)hipFree(c->tm);
     if (c->mt) (void)hipFree(c->mt);
@@ -607,6 +619,62 @@ int qsmd_table_set(qsmd_ctx* c, const qsmd_table_model* m) {
     return QSMD_OK;
 }
 
+int qsmd_wtable_set(qsmd_ctx* c, const qsmd_wtable_model* m) {
+    if (!c) return QSMD_ERR_ARG;
+    std::lock_guard<std::mutex> g(c->mu);
+    if (!m || !m->on_inv || !m->on_resp || !m->post) return fail(c, QSMD_ERR_ARG, "qsmd_wtable_set: null table");
+    if (m->n_states == 0 || m->n_states > QSMD_WTABLE_MAX_STATES || m->n_inv == 0 || m->n_inv > QSMD_WTABLE_MAX_INV ||
+        m->n_resp == 0 || m->n_resp > QSMD_WTABLE_MAX_RESP)
+        return fail(c, QSMD_ERR_ARG, "qsmd_wtable_set: dimensions outside 1..65536 states, 1..256 symbols");
+    WTableDev t{};
+    t.n_states = m->n_states;
+    t.n_inv = m->n_inv;
+    t.n_resp = m->n_resp;
+    t.has_err = m->post_err ? 1u : 0u;
+    t.post_words = (m->n_resp + 31u) / 32u;
+    t.rec_words = 1u + t.post_words * (t.has_err ? 2u : 1u);
+    // (before anything is read or copied: at most 2^24 records of 17 words)
+    const uint64_t si = (uint64_t)m->n_states * m->n_inv, sr = (uint64_t)m->n_states * m->n_resp;
+    const uint64_t words = (si * t.rec_words + (sr + 1u) / 2u + 3u) / 4u * 4u;
+    if (words * 4u > QSMD_WTABLE_MAX_BYTES)
+        return fail(c, QSMD_ERR_ARG, "qsmd_wtable_set: the tables exceed QSMD_WTABLE_MAX_BYTES");
+    if (m->init_state >= m->n_states) return fail(c, QSMD_ERR_ARG, "qsmd_wtable_set: init_state >= n_states");
+    for (uint64_t k = 0; k < si; ++k)
+        if (m->on_inv[k] >= m->n_states) return fail(c, QSMD_ERR_ARG, "qsmd_wtable_set: on_inv entry >= n_states");
+    for (uint64_t k = 0; k < sr; ++k)
+        if (m->on_resp[k] >= m->n_states) return fail(c, QSMD_ERR_ARG, "qsmd_wtable_set: on_resp entry >= n_states");
+    t.blob_words = (uint32_t)words;
+    t.on_resp_off = (uint32_t)(si * t.rec_words);
+    // (bits at or above n_resp are never read: the kernel checks every code)
+    std::vector<uint32_t> blob(t.blob_words, 0u);
+    for (uint64_t k = 0; k < si; ++k) {
+        uint32_t* rec = blob.data() + k * t.rec_words;
+        rec[0] = m->on_inv[k];
+        std::memcpy(rec + 1, m->post + k * t.post_words, (size_t)t.post_words * 4);
+        if (m->post_err) std::memcpy(rec + 1 + t.post_words, m->post_err + k * t.post_words, (size_t)t.post_words * 4);
+    }
+    std::memcpy(blob.data() + t.on_resp_off, m->on_resp, (size_t)sr * 2);
+    HIP_TRY(c, hipSetDevice(c->device), "hipSetDevice");
+    uint32_t* dev = nullptr;
+    hipError_t e = hipMalloc(reinterpret_cast<void**>(&dev), (size_t)t.blob_words * 4);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(c, QSMD_ERR_NOMEM, "hipMalloc", e);
+    }
+    e = hipMemcpy(dev, blob.data(), (size_t)t.blob_words * 4, hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        (void)hipFree(dev);
+        return fail(c, QSMD_ERR_DEVICE, "H2D table", e);
+    }
+    quiesce(c);                         // the last call may still read the old table
+    if (c->wtab_blob) (void)hipFree(c->wtab_blob);
+    t.blob = dev;
+    c->wtab_blob = dev;
+    c->wtab = t;
+    c->wtab_init = m->init_state;
+    return QSMD_OK;
+}
+
 int qsmd_set_time_limit_ms(qsmd_ctx* c, uint64_t ms) {
     if (!c) return QSMD_ERR_ARG;
     c->time_limit_ms = ms;
@@ -730,17 +798,26 @@ enum : uint32_t { kClassesKnown = 8u };
 // One QSMD_MODEL_TABLE call (csrc/table.hip): the binning kernel, per width
 // class pass 1 and (with a budget) pass 2, the totals -- on one stream, no
 // host round trip.  The cascade's workspace and knobs are not touched.
+// WIDE: a QSMD_MODEL_WTABLE call (csrc/wtable.hip), the same launches over
+// the context's wide table.
+extern "C++" {
+template <bool WIDE>
 static int check_table_locked(qsmd_ctx* c, const qsmd_hdr* hdr, uint64_t n_hist, const qsmd_event* events,
                               uint64_t n_events, const void* model0, uint32_t flags, uint64_t max_nodes,
                               uint8_t* status, uint64_t* nodes, uint8_t* witness, qsmd_totals* totals,
                               hipStream_t s, uint32_t route) {
     if (flags & QSMD_FLAG_EARLY_EXIT_BATCH)
-        return fail(c, QSMD_ERR_UNSUPPORTED, "QSMD_FLAG_EARLY_EXIT_BATCH: not for QSMD_MODEL_TABLE");
-    if (!c->tab_blob) return fail(c, QSMD_ERR_ARG, "QSMD_MODEL_TABLE: no table set (qsmd_table_set)");
+        return fail(c, QSMD_ERR_UNSUPPORTED, "QSMD_FLAG_EARLY_EXIT_BATCH: not for the table models");
+    if constexpr (WIDE) {
+        if (!c->wtab_blob) return fail(c, QSMD_ERR_ARG, "QSMD_MODEL_WTABLE: no table set (qsmd_wtable_set)");
+    } else {
+        if (!c->tab_blob) return fail(c, QSMD_ERR_ARG, "QSMD_MODEL_TABLE: no table set (qsmd_table_set)");
+    }
     if (n_hist && (!hdr || !status)) return fail(c, QSMD_ERR_ARG, "null hdr/status");
     if (n_hist > 0xFFFFFFFFull) return fail(c, QSMD_ERR_ARG, "n_hist > 2^32-1");
-    const uint32_t state0 = model0 ? *static_cast<const uint32_t*>(model0) : c->tab_init;
-    if (state0 >= c->tab.n_states) return fail(c, QSMD_ERR_ARG, "model0: state >= n_states");
+    const uint32_t state0 = model0 ? *static_cast<const uint32_t*>(model0) : (WIDE ? c->wtab_init : c->tab_init);
+    if (state0 >= (WIDE ? c->wtab.n_states : c->tab.n_states))
+        return fail(c, QSMD_ERR_ARG, "model0: state >= n_states");
     HIP_TRY(c, hipSetDevice(c->device), "hipSetDevice");
     HIP_TRY(c, order_after_previous(c, s), "order after the previous call");
 
@@ -749,13 +826,13 @@ static int check_table_locked(qsmd_ctx* c, const qsmd_hdr* hdr, uint64_t n_hist,
     int rc = grow(c, &c->tws, &c->tws_bytes, off_tot + align_up(sizeof(qsmd_totals)));
     if (rc) return rc;
     HIP_TRY(c, hipMemsetAsync(c->tws, 0, kTabHeader, s), "memset header");
-    TableArgs p{};
+    std::conditional_t<WIDE, WTableArgs, TableArgs> p{};
     p.s.hdr = hdr;
     p.s.events = reinterpret_cast<const uint2*>(events);
     p.s.n_hist = n_hist;
     p.s.n_events = n_events;
     p.s.flags = flags;
-    p.s.model_id = QSMD_MODEL_TABLE;
+    p.s.model_id = WIDE ? QSMD_MODEL_WTABLE : QSMD_MODEL_TABLE;
     p.s.max_nodes = max_nodes;
     p.s.time_limit = c->time_limit_ms * 100000ull;   // 100 MHz s_memrealtime
     p.s.status = status;
@@ -764,7 +841,7 @@ static int check_table_locked(qsmd_ctx* c, const qsmd_hdr* hdr, uint64_t n_hist,
     p.s.buckets = reinterpret_cast<unsigned long long*>(c->tws + kTabOffBuckets);
     p.cnt = reinterpret_cast<uint32_t*>(c->tws);
     p.s.timed_out = p.cnt + TC_TIMED;
-    p.t = c->tab;
+    if constexpr (WIDE) p.t = c->wtab; else p.t = c->tab;
     p.state0 = state0;
     for (int k = 0; k < 3; ++k) {
         p.class_list[k] = reinterpret_cast<uint32_t*>(c->tws + kTabHeader + (size_t)k * lst);
@@ -776,9 +853,10 @@ static int check_table_locked(qsmd_ctx* c, const qsmd_hdr* hdr, uint64_t n_hist,
     // grids: every kernel is grid-stride over a count read on the device, so
     // any grid gives the same results.  One workgroup per group of 64 while
     // the tables are small (each workgroup copies them to LDS), else a few per
-    // CU; pass 2 from the last table call's count.
+    // CU (the wide tables are not copied: always one per group); pass 2 from
+    // the last table call's count.
     const uint64_t groups = std::max<uint64_t>((n_hist + 63) / 64, 1);
-    const uint64_t cap1 = (size_t)c->tab.blob_words * 4 <= 4096 ? 65536ull : 8ull * c->n_cu;
+    const uint64_t cap1 = WIDE || (size_t)c->tab.blob_words * 4 <= 4096 ? 65536ull : 8ull * c->n_cu;
     const uint64_t last2 = c->probe_host[kProbeTabPass2];
     // (at least 16 per CU: a workgroup with no group to search returns at
     // once, and the first call has no count -- on 256 workgroups its pass 2
@@ -816,14 +894,20 @@ static int check_table_locked(qsmd_ctx* c, const qsmd_hdr* hdr, uint64_t n_hist,
             }
             c->tm_bytes = need;
             HIP_TRY(c, hipMemsetAsync(c->tm, 0, c->tm_bytes, s), "memset table memo");
-        }
-        if (((++c->tm_epoch) & 0xFFFFFFu) == 0u) {   // 24-bit tags wrapped: clear
+        } else if (c->tm_wide != WIDE) {    // the other path's entries: their tag word reads differently
             HIP_TRY(c, hipMemsetAsync(c->tm, 0, c->tm_bytes, s), "memset table memo");
-            ++c->tm_epoch;
+        }
+        c->tm_wide = WIDE;
+        // (narrow: 24-bit epochs beside an 8-bit state; wide: 16 beside 16)
+        uint32_t& epoch = WIDE ? c->tm_epoch_w : c->tm_epoch;
+        constexpr uint32_t kEpochMask = WIDE ? 0xFFFFu : 0xFFFFFFu;
+        if (((++epoch) & kEpochMask) == 0u) {        // the tags wrapped: clear
+            HIP_TRY(c, hipMemsetAsync(c->tm, 0, c->tm_bytes, s), "memset table memo");
+            ++epoch;
         }
         p.memo = reinterpret_cast<uint4*>(c->tm);
         p.memo_entries = (uint32_t)c->table_memo;
-        p.memo_epoch = c->tm_epoch & 0xFFFFFFu;
+        p.memo_epoch = epoch & kEpochMask;
         for (int k = 0; k < 3; ++k) grid2[k] = (uint32_t)gm;
     }
     HIP_TRY(c, launch_table(p, grid1, grid2, (route & kClassesKnown) ? (route & 7u) : 7u, s), "table launch");
@@ -834,14 +918,18 @@ static int check_table_locked(qsmd_ctx* c, const qsmd_hdr* hdr, uint64_t n_hist,
     c->in_flight = true;
     return QSMD_OK;
 }
+}  // extern "C++"
 
 static int check_device_locked(qsmd_ctx* c, uint32_t model_id, const qsmd_hdr* hdr, uint64_t n_hist,
                                const qsmd_event* events, uint64_t n_events, const void* model0,
                                uint32_t flags, uint64_t max_nodes, uint8_t* status, uint64_t* nodes,
                                uint8_t* witness, qsmd_totals* totals, hipStream_t s, uint32_t route = 0u) {
+    if (model_id == QSMD_MODEL_WTABLE)
+        return check_table_locked<true>(c, hdr, n_hist, events, n_events, model0, flags, max_nodes, status, nodes,
+                                        witness, totals, s, route);
     if (model_id == QSMD_MODEL_TABLE)
-        return check_table_locked(c, hdr, n_hist, events, n_events, model0, flags, max_nodes, status, nodes,
-                                  witness, totals, s, route);
+        return check_table_locked<false>(c, hdr, n_hist, events, n_events, model0, flags, max_nodes, status, nodes,
+                                         witness, totals, s, route);
     if (model_id != QSMD_MODEL_BANK && model_id != QSMD_MODEL_TICKET)
         return fail(c, QSMD_ERR_ARG, "unknown model_id");
     if (n_hist && (!hdr || !status)) return fail(c, QSMD_ERR_ARG, "null hdr/status");
@@ -1296,7 +1384,8 @@ int qsmd_check_batch(qsmd_ctx* c, uint32_t model_id, const qsmd_hdr* hdr, uint64
         fits0w = fits0w || (few && hdr[i].n_ev <= 64u);
     }
     uint32_t route = n_hist == 0 ? 0u : (fits0 ? 0u : kSkip0) | (fits0w || fits0 ? 0u : kSkip0w);
-    if (model_id == QSMD_MODEL_TABLE) {     // the width classes present: one launch per non-empty class
+    // the table models: the width classes present (one launch per non-empty class)
+    if (model_id == QSMD_MODEL_TABLE || model_id == QSMD_MODEL_WTABLE) {
         route = kClassesKnown;
         for (uint64_t i = 0; i < n_hist && (route & 7u) != 7u; ++i)
             route |= hdr[i].n_ev <= 32u ? 1u : (hdr[i].n_ev <= 64u ? 2u : 4u);
@@ -1525,7 +1614,8 @@ int qsmd_split_frontier(qsmd_ctx* c, uint32_t model_id, const qsmd_hdr* hdr, con
     if (!c) return QSMD_ERR_ARG;
     if (!hdr || !fr || (max_tasks && !tasks_out) || (n_events && !events))
         return fail(c, QSMD_ERR_ARG, "null argument");
-    if (model_id == QSMD_MODEL_TABLE) return fail(c, QSMD_ERR_UNSUPPORTED, "split search: not for QSMD_MODEL_TABLE");
+    if (model_id == QSMD_MODEL_TABLE || model_id == QSMD_MODEL_WTABLE)
+        return fail(c, QSMD_ERR_UNSUPPORTED, "split search: not for the table models");
     if (model_id != QSMD_MODEL_BANK && model_id != QSMD_MODEL_TICKET) return fail(c, QSMD_ERR_ARG, "unknown model_id");
     if (max_tasks > (1ull << 24)) return fail(c, QSMD_ERR_ARG, "max_tasks > 2^24");
     std::lock_guard<std::mutex> g(c->mu);
@@ -1603,7 +1693,8 @@ int qsmd_check_tasks(qsmd_ctx* c, uint32_t model_id, const qsmd_hdr* hdr, const 
     if (!c) return QSMD_ERR_ARG;
     if (!hdr || (n_tasks && (!tasks || !status_out)) || (n_events && !events))
         return fail(c, QSMD_ERR_ARG, "null argument");
-    if (model_id == QSMD_MODEL_TABLE) return fail(c, QSMD_ERR_UNSUPPORTED, "split search: not for QSMD_MODEL_TABLE");
+    if (model_id == QSMD_MODEL_TABLE || model_id == QSMD_MODEL_WTABLE)
+        return fail(c, QSMD_ERR_UNSUPPORTED, "split search: not for the table models");
     if (model_id != QSMD_MODEL_BANK && model_id != QSMD_MODEL_TICKET) return fail(c, QSMD_ERR_ARG, "unknown model_id");
     if (n_tasks > (1ull << 24)) return fail(c, QSMD_ERR_ARG, "n_tasks > 2^24");
     if (hdr->model_id != model_id || !split_hdr_ok(hdr, n_events)) return fail(c, QSMD_ERR_ARG, "bad history header");

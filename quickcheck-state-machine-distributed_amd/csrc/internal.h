@@ -430,6 +430,43 @@ hipError_t launch_table(const TableArgs& p, const uint32_t grid1[3], const uint3
 // (memo: pass 2 with the state memo, + 8 B per level and lane)
 size_t table_lds_bytes(const TableDev& t, int k, bool memo = false);
 
+// QSMD_MODEL_WTABLE (csrc/wtable.hip): the same search for up to 65,536
+// states and 256 symbols; the tables stay in device memory.  The context's
+// copy is one blob of 32-bit words, read-only while a call runs:
+//   n_states * n_inv records of rec_words words, record (s, i) =
+//     on_inv[s][i] | post[s][i][0 .. post_words) | post_err[s][i][0 .. post_words) (when given)
+//   then on_resp [n_states * n_resp] u16 (at word on_resp_off).
+// The three words a step needs from (s, i) are next to each other (one cache
+// line unless the record straddles two), and independent of each other.
+struct WTableDev {
+    const uint32_t* blob;         // device
+    uint32_t blob_words;
+    uint32_t n_states, n_inv, n_resp;
+    uint32_t has_err;             // post_err present
+    uint32_t post_words;          // ceil(n_resp / 32)
+    uint32_t rec_words;           // 1 + post_words * (has_err ? 2 : 1)
+    uint32_t on_resp_off;         // word offset of on_resp
+};
+// TableArgs with the wide table; the workspace, the counters (TCnt) and the
+// probe slots are the narrow path's.  memo_epoch: 16 bits (the state has the
+// low 16 of the entry's tag word).
+struct WTableArgs {
+    SearchArgs s;
+    WTableDev t;
+    uint32_t state0;
+    uint32_t* cnt;
+    uint32_t* class_list[3];
+    uint32_t* heavy_list[3];
+    uint64_t budget;
+    qsmd_totals* totals;
+    uint32_t* probe_host;
+    uint4* memo;
+    uint32_t memo_entries;
+    uint32_t memo_epoch;
+};
+hipError_t launch_table(const WTableArgs& p, const uint32_t grid1[3], const uint32_t grid2[3], uint32_t classes,
+                        hipStream_t s);
+
 // Early exit: relaxed agent-scope read (a stale value only delays skipping).
 __device__ __forceinline__ bool beyond_first_fail(const SearchArgs& a, uint32_t h) {
     return a.first_fail && h > __hip_atomic_load(a.first_fail, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);

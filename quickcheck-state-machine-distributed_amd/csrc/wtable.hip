@@ -1,41 +1,24 @@
-// table.hip -- QSMD_MODEL_TABLE: the reference search for a finite-state
-// model given as tables at run time (include/qsmd.h qsmd_table_model).
-//
-// The reference's `linearisable` takes any transition / postcondition
-// closures (src/Linearisability.hs:52-58); a C ABI cannot.  A model with at
-// most 256 states and 32 invocation / response symbols is four tables, and a
-// step from state s with invocation i and response r is
-//     post  = bit r of post[s][i]            (postcondition m inv resp)
-//     raise = bit r of post_err[s][i]        (the postcondition raises)
-//     next  = on_resp[on_inv[s][i]][r]       (transition twice, :63-65)
-//
-// One lane per history runs the reference DFS over the Lemma L1 event bitset
-// (SURVEY.md §8a), as the compact stages do (lane.h LaneDFS), but for any
-// history the encoding holds: up to 128 events, 128 pids, shared pids.  The
-// pids are bit-sliced into seven mask planes (lane.h slices three).  Nothing
-// of the hot loop is in global memory:
-//   * the tables are copied to LDS by every workgroup (dynamic size: the
-//     table actually set; 80 KB at 256 x 32 x 32 with post_err);
-//   * a history's events are 16 bits each (pid 7 | kind 1 | code 8: the low
-//     half of the event's first word), the DFS stack 16 bits per level
-//     (chosen event 8 | state before the step 8).  Both are stored two to a
-//     32-bit word, [x / 2][lane][x & 1]: the word a lane touches is in bank
-//     lane % 32 whatever x is, so the per-lane indexed 16-bit reads and
-//     writes of a divergent wavefront are conflict-free ([x][lane] with
-//     16-bit elements would put lanes 2k and 2k + 1 on one bank with
-//     different rows: a 2-way conflict);
-//   * undo restores the remaining set by Lemma L1 (the last removed events
-//     of the pid are the highest removed ones) and the state from the stack.
-//
-// Three width classes (32-, 64-, 128-event masks) so a batch of short
-// histories pays neither M128 masks nor 128-event LDS: table_bin sorts the
-// headers into three index lists (wave_append), one launch per class.  Each
-// class runs two passes: pass 1 with a node budget ("table_budget"), a search
-// over it appended to the class's heavy list; pass 2 grid-stride over that
-// list (count read on the device), each history searched again from the root
-// -- so the node counts stay the reference's.  With the knob "table_memo"
-// pass 2 runs the MEMO instantiation: an exact-count state memo per lane slot
-// (TableMemo, table_lane.h; the counts, the verdict and the witness are unchanged).
+// wtable.hip -- QSMD_MODEL_WTABLE: table.hip's search for a model too large
+// for LDS (include/qsmd.h qsmd_wtable_model): up to 65,536 states, 256
+// invocation and 256 response symbols.  The semantics are model 3's,
+//     post  = bit r of post[s][i]            (word r >> 5, bit r & 31)
+//     raise = bit r of post_err[s][i]
+//     next  = on_resp[on_inv[s][i]][r]
+// and so is the structure: one lane per history over the Lemma L1 bitsets and
+// seven pid planes (table_lane.h), three width classes, pass 1 with
+// "table_budget", pass 2 grid-stride over the heavy list from the root, the
+// optional state memo, a finish kernel.  Three things differ:
+//   * the tables are read from device memory (internal.h WTableDev: one
+//     record per (state, invocation) holding on_inv and the postcondition
+//     words).  Given (state, i, rc) the record's on_inv word, its post word
+//     rc >> 5 and (only when the model has one) its post_err word are
+//     independent loads issued together; on_resp is the one dependent load;
+//   * a state has 16 bits, so the DFS stack is one 32-bit word per level
+//     (event 8 | state before the step 16), [level][lane]: bank lane % 32
+//     whatever the level.  The events stay 16 bits in col16's paired words;
+//   * the memo's tag word is epoch 16 | state 16 (table.hip: 24 | 8).
+// LDS per workgroup: 4 / 8 / 16 KB of events and as much of stack (with the
+// memo, 8 / 16 / 32 KB of node counts more); no table.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -49,26 +32,18 @@ namespace qsmd {
 
 namespace {
 
-using namespace tlane;     // the width classes, mask helpers, col16, stage_table, TableMemo
+using namespace tlane;
 
-struct TabLds {
-    const uint32_t* post;
-    const uint32_t* post_err;     // null: none
-    const uint8_t* on_inv;
-    const uint8_t* on_resp;
-};
-
-// One lane's search state (registers) over its LDS columns.
+// One lane's search state (registers) over its LDS columns: table.hip's
+// TableDFS with the wide step.
 template <class M>
-struct TableDFS {
+struct WTableDFS {
     using MO = MaskOps<M>;
     M INV, RESP, P[7];
     M rem, cand;
     uint32_t state, depth, found;
     uint64_t nodes;
 
-    // the events of event j's pid (the bits beyond the history are junk:
-    // every use ANDs with INV or RESP)
     __device__ __forceinline__ M same_pid(uint32_t j) const {
         M acc = t_ones<M>();
 #pragma unroll
@@ -91,29 +66,21 @@ struct TableDFS {
                                : ((!found && depth > 0) ? QSMD_STATUS_LINEARISABLE : QSMD_STATUS_NONLINEARISABLE);
     }
 
-    // One iteration, as LaneDFS::step: an optional backtrack, then one
-    // candidate.  -1 = go on, kTerm = the search ended (finish()), or
-    // QSMD_STATUS_BUDGET (limit nodes counted; nothing moved) /
+    // One iteration: TableDFS::step with the tables in device memory and the
+    // 32-bit stack.  Returns -1 = go on, kTerm, QSMD_STATUS_BUDGET or
     // QSMD_STATUS_MODEL_ERROR.
-    // MEMO (pass 2 with "table_memo"): a subtree left by a backtrack is
-    // recorded with the nodes it counted, a descent into a recorded state
-    // counts them and backtracks at once (the rule of memo.hip's memo_step).
     template <bool MEMO>
-    __device__ __forceinline__ int step(const TableDev& t, const TabLds& L, const uint16_t* ev, uint16_t* stk,
-                                        int lane, uint64_t limit, TableMemo<M>& mm) {
+    __device__ __forceinline__ int step(const WTableDev& t, const uint16_t* on_resp, const uint16_t* ev,
+                                        uint32_t* stk, int lane, uint64_t limit, TableMemo<M>& mm) {
         const bool empty = !MO::any(cand);
-        // no children: a leaf => True (any' []), the root => False (any [])
         if (empty && (found == 0u || depth == 0u)) return kTerm;
         if (empty) {
-            // backtrack: the parent's remaining set by Lemma L1, its state
-            // from the stack
             --depth;
             if constexpr (MEMO) {
-                // (rem, state) are still the node's being left
                 if (!mm.skip) mm.record(rem, state, nodes - mm.entry[depth * C_LANES]);
                 mm.skip = false;
             }
-            const uint32_t st = stk[col16(depth, lane)];
+            const uint32_t st = stk[depth * C_LANES + lane];
             const uint32_t j = st & 0xFFu;
             state = st >> 8;
             const M gone = ~rem & same_pid(j);
@@ -130,17 +97,20 @@ struct TableDFS {
         if (nodes >= limit) return QSMD_STATUS_BUDGET;
         const uint32_t r = (uint32_t)MO::ctz(rr);
         const uint32_t i = ev[col16(j, lane)] >> 8, rc = ev[col16(r, lane)] >> 8;
-        const uint32_t idx = state * t.n_inv + i;
-        const uint32_t ok = (L.post[idx] >> rc) & 1u;
-        const uint32_t err = L.post_err ? (L.post_err[idx] >> rc) & 1u : 0u;
+        // the record of (state, i): three independent loads, post_err's only
+        // when the model has one (a uniform condition)
+        const uint32_t* rec = t.blob + (state * t.n_inv + i) * t.rec_words;
+        const uint32_t w = rc >> 5, b = rc & 31u;
+        const uint32_t mid = rec[0];
+        const uint32_t pw = rec[1u + w];
+        const uint32_t ew = t.has_err ? rec[1u + t.post_words + w] : 0u;
         ++nodes;
         found = 1u;
-        if (err) return QSMD_STATUS_MODEL_ERROR;
-        if (ok) {
-            stk[col16(depth, lane)] = (uint16_t)(j | (state << 8));
+        if ((ew >> b) & 1u) return QSMD_STATUS_MODEL_ERROR;
+        if ((pw >> b) & 1u) {
+            stk[depth * C_LANES + lane] = j | (state << 8);
             ++depth;
-            state = L.on_resp[(uint32_t)L.on_inv[idx] * t.n_resp + rc];
-            // the pid's first remaining invocation (quirk Q1: not always j) and response
+            state = on_resp[mid * t.n_resp + rc];
             rem = rem & ~(MO::lowest(rem & pmj & INV) | MO::bit((int)r));
             cand = t_cands(rem, INV, RESP);
             found = 0u;
@@ -165,9 +135,8 @@ struct TableDFS {
     }
 };
 
-// Sort the headers into the three class lists; the histories decided from
-// the header alone get their result here.
-__global__ __launch_bounds__(C_LANES) void table_bin(TableArgs a) {
+// table.hip's table_bin for model id 4
+__global__ __launch_bounds__(C_LANES) void wtable_bin(WTableArgs a) {
     const int lane = threadIdx.x;
     WaveCounters cnt;
     for (uint64_t base = (uint64_t)blockIdx.x * C_LANES; base < a.s.n_hist; base += (uint64_t)gridDim.x * C_LANES) {
@@ -175,7 +144,7 @@ __global__ __launch_bounds__(C_LANES) void table_bin(TableArgs a) {
         const bool active = h < a.s.n_hist;
         qsmd_hdr H{0, 0, 0, 0, 0, 0};
         if (active) H = a.s.hdr[h];
-        const bool enc_ok = H.model_id == QSMD_MODEL_TABLE && H.n_ev <= QSMD_MAX_EVENTS &&
+        const bool enc_ok = H.model_id == QSMD_MODEL_WTABLE && H.n_ev <= QSMD_MAX_EVENTS &&
                             (uint64_t)H.ev_off + H.n_ev <= a.s.n_events;
         const bool out = active && (!enc_ok || H.n_ev == 0);
         const int status = enc_ok ? QSMD_STATUS_LINEARISABLE : QSMD_STATUS_ENCODE_ERROR;   // src/Linearisability.hs:59
@@ -192,12 +161,11 @@ __global__ __launch_bounds__(C_LANES) void table_bin(TableArgs a) {
     cnt.flush(a.s.buckets, lane);
 }
 
-// PASS2 false: the class list with the pass-1 budget; true: the class's
-// heavy list, every search to its end.
-// MEMO: pass 2 with the state memo (a.memo: one table of a.memo_entries
-// entries per lane slot of the grid).
+// table.hip's table_search: PASS2 false = the class list with the pass-1
+// budget, true = the class's heavy list to the end; MEMO = pass 2 with the
+// state memo.
 template <class M, bool MEMO>
-__global__ __launch_bounds__(C_LANES) void table_search(TableArgs a, uint32_t pass2) {
+__global__ __launch_bounds__(C_LANES) void wtable_search(WTableArgs a, uint32_t pass2) {
     constexpr int EV = TW<M>::EV, K = TW<M>::CLASS;
     extern __shared__ uint32_t lds[];
     const int lane = threadIdx.x;
@@ -205,30 +173,19 @@ __global__ __launch_bounds__(C_LANES) void table_search(TableArgs a, uint32_t pa
     const uint32_t total = a.cnt[(pass2 ? TC_HEAVY : TC_CLASS) + K];
     if ((uint64_t)blockIdx.x * C_LANES >= total) return;
 
-    // LDS: events [EV / 2][64] words, stack [EV / 4][64] words, (MEMO: the
-    // node counts at entry, [EV / 2][64] u64,) the tables
+    // LDS: events [EV / 2][64] words, stack [EV / 2][64] words, (MEMO: the
+    // node counts at entry, [EV / 2][64] u64)
     uint16_t* ev = reinterpret_cast<uint16_t*>(lds);
-    uint16_t* stk = reinterpret_cast<uint16_t*>(lds + (EV / 2) * C_LANES);
-    uint32_t* tab = lds + (EV / 2 + EV / 4 + (MEMO ? EV : 0)) * C_LANES;
+    uint32_t* stk = lds + (EV / 2) * C_LANES;
     TableMemo<M> mm;
     if constexpr (MEMO) {
-        mm.entry = reinterpret_cast<uint64_t*>(lds + (EV / 2 + EV / 4) * C_LANES) + lane;
+        mm.entry = reinterpret_cast<uint64_t*>(lds + EV * C_LANES) + lane;
         mm.tab = a.memo + ((uint64_t)blockIdx.x * C_LANES + (uint64_t)lane) * (uint64_t)a.memo_entries * 2ull;
         mm.mask = a.memo_entries - 1u;
-        mm.tag = a.memo_epoch << 8;
+        mm.tag = a.memo_epoch << 16;
         mm.hits = 0u;
     }
-    {
-        const uint4* src = reinterpret_cast<const uint4*>(a.t.blob);
-        uint4* dst = reinterpret_cast<uint4*>(tab);
-        for (uint32_t k = lane; k < a.t.blob_words / 4u; k += C_LANES) dst[k] = src[k];
-    }
-    __syncthreads();
-    TabLds L;
-    L.post = tab;
-    L.post_err = a.t.has_err ? tab + table_off_err(a.t) : nullptr;
-    L.on_inv = reinterpret_cast<const uint8_t*>(tab + table_off_inv(a.t));
-    L.on_resp = reinterpret_cast<const uint8_t*>(tab + table_off_resp(a.t));
+    const uint16_t* on_resp = reinterpret_cast<const uint16_t*>(a.t.blob + a.t.on_resp_off);
 
     WaveCounters cnt;
     const uint64_t t0 = a.s.time_limit ? __builtin_amdgcn_s_memrealtime() : 0;
@@ -242,7 +199,7 @@ __global__ __launch_bounds__(C_LANES) void table_search(TableArgs a, uint32_t pa
         const uint32_t h = active ? list[idx] : 0u;
         qsmd_hdr H{0, 0, 0, 0, 0, 0};
         if (active) H = a.s.hdr[h];
-        TableDFS<M> dfs;
+        WTableDFS<M> dfs;
         dfs.depth = 0;
         dfs.nodes = 0;
         dfs.found = 0;
@@ -257,7 +214,7 @@ __global__ __launch_bounds__(C_LANES) void table_search(TableArgs a, uint32_t pa
         // wavefront-uniform counter: the loop runs while any lane searches)
         while (__ballot(status == -1) != 0ull) {
             for (uint32_t k = 0; k < 1024u; ++k) {
-                if (status == -1) status = dfs.template step<MEMO>(a.t, L, ev, stk, lane, limit, mm);
+                if (status == -1) status = dfs.template step<MEMO>(a.t, on_resp, ev, stk, lane, limit, mm);
                 if (__ballot(status == -1) == 0ull) break;
             }
             if (status == -1 && a.s.time_limit && __builtin_amdgcn_s_memrealtime() - t0 > a.s.time_limit) {
@@ -275,7 +232,7 @@ __global__ __launch_bounds__(C_LANES) void table_search(TableArgs a, uint32_t pa
             if (a.s.nodes) a.s.nodes[h] = dfs.nodes;
             if (a.s.witness && status == QSMD_STATUS_LINEARISABLE) {
                 uint8_t* w = a.s.witness + H.ev_off;
-                for (uint32_t d = 0; d < dfs.depth; ++d) w[d] = (uint8_t)(stk[col16(d, lane)] & 0xFFu);
+                for (uint32_t d = 0; d < dfs.depth; ++d) w[d] = (uint8_t)(stk[d * C_LANES + lane] & 0xFFu);
                 if (dfs.depth < H.n_ev) w[dfs.depth] = QSMD_WITNESS_END;
             }
         }
@@ -292,8 +249,9 @@ __global__ __launch_bounds__(C_LANES) void table_search(TableArgs a, uint32_t pa
     cnt.flush(a.s.buckets, lane);
 }
 
-// The call's totals from the buckets, the probe for the host.
-__global__ __launch_bounds__(C_LANES) void table_finish(TableArgs a) {
+// The call's totals from the buckets, the probe for the host (table.hip's
+// table_finish).
+__global__ __launch_bounds__(C_LANES) void wtable_finish(WTableArgs a) {
     const uint32_t k = threadIdx.x;
     if (k < (uint32_t)T_N) {
         uint64_t v = 0;
@@ -310,30 +268,21 @@ __global__ __launch_bounds__(C_LANES) void table_finish(TableArgs a) {
     }
 }
 
+// (at most 64 KB, the 128-event class with the memo: no attribute to raise)
 template <class M, bool MEMO>
-hipError_t launch_class(const TableArgs& p, uint32_t grid, uint32_t pass2, hipStream_t s) {
-    const size_t lds = table_lds_bytes(p.t, TW<M>::CLASS, MEMO);
-    if (lds > 64u * 1024u) {
-        static std::atomic<int> set[kAttrDevices];
-        const hipError_t e = ensure_dyn_lds(reinterpret_cast<const void*>(&table_search<M, MEMO>), set, lds);
-        if (e != hipSuccess) return e;
-    }
-    hipLaunchKernelGGL((table_search<M, MEMO>), dim3(grid), dim3(C_LANES), lds, s, p, pass2);
+hipError_t launch_class(const WTableArgs& p, uint32_t grid, uint32_t pass2, hipStream_t s) {
+    constexpr size_t lds = (size_t)(TW<M>::EV + (MEMO ? TW<M>::EV : 0)) * C_LANES * 4;
+    static_assert(lds <= 64u * 1024u, "dynamic LDS within the default limit");
+    hipLaunchKernelGGL((wtable_search<M, MEMO>), dim3(grid), dim3(C_LANES), lds, s, p, pass2);
     return hipGetLastError();
 }
 
 }  // namespace
 
-size_t table_lds_bytes(const TableDev& t, int k, bool memo) {
-    const size_t ev = k == 0 ? 32 : (k == 1 ? 64 : 128);
-    return ((ev / 2 + ev / 4 + (memo ? ev : 0)) * C_LANES + (size_t)t.blob_words) * 4;
-}
-
-hipError_t launch_table(const TableArgs& p, const uint32_t grid1[3], const uint32_t grid2[3], uint32_t classes,
+hipError_t launch_table(const WTableArgs& p, const uint32_t grid1[3], const uint32_t grid2[3], uint32_t classes,
                         hipStream_t s) {
-    static_assert(sizeof(qsmd_totals) == T_N * 8, "qsmd_totals is T_N x u64 in T_* order");
     const uint32_t gb = (uint32_t)std::min<uint64_t>(std::max<uint64_t>((p.s.n_hist + 63) / 64, 1), 4096);
-    hipLaunchKernelGGL(table_bin, dim3(gb), dim3(C_LANES), 0, s, p);
+    hipLaunchKernelGGL(wtable_bin, dim3(gb), dim3(C_LANES), 0, s, p);
     hipError_t e = hipGetLastError();
     for (uint32_t pass2 = 0; pass2 < (p.budget ? 2u : 1u) && e == hipSuccess; ++pass2) {
         const uint32_t* g = pass2 ? grid2 : grid1;
@@ -348,7 +297,7 @@ hipError_t launch_table(const TableArgs& p, const uint32_t grid1[3], const uint3
         if (e == hipSuccess && (classes & 4u)) e = launch_class<M128, false>(p, g[2], pass2, s);
     }
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(table_finish, dim3(1), dim3(C_LANES), 0, s, p);
+    hipLaunchKernelGGL(wtable_finish, dim3(1), dim3(C_LANES), 0, s, p);
     return hipGetLastError();
 }
 

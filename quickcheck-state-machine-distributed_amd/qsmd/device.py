@@ -61,6 +61,7 @@ EXPORTS = {
     "qsmd_last_error": (ctypes.c_char_p, [_P]),
     "qsmd_set_time_limit_ms": (_I, [_P, _U64]),
     "qsmd_table_set": (_I, [_P, _P]),
+    "qsmd_wtable_set": (_I, [_P, _P]),
     "qsmd_set_stage0_grid": (_I, [_P, _U64]),
     "qsmd_set_stage0_budget": (_I, [_P, _U64]),
     "qsmd_probe_read": (_I, [_P, _P]),
@@ -153,6 +154,7 @@ class Context:
         self._lib = lib
         self._check_fn = ctypes.cast(lib.qsmd_check_batch, ctypes.c_void_p).value
         self._table = None              # the models.TableModel this context holds (set_table)
+        self._wide_table = None         # the models.WideTableModel it holds (set_wide_table)
         if time_limit_ms is not None:
             lib.qsmd_set_time_limit_ms(h, int(time_limit_ms))
 
@@ -237,9 +239,22 @@ class Context:
         """The models.TableModel set last (None: none)."""
         return self._table
 
+    def set_wide_table(self, model):
+        """qsmd_wtable_set: make ``model`` (a models.WideTableModel) the
+        context's table for QSMD_MODEL_WTABLE calls; a context holds one wide
+        table, beside the narrow one."""
+        st = model.c_struct()
+        self._check(self._lib.qsmd_wtable_set(self._h, ctypes.byref(st)), "qsmd_wtable_set")
+        self._wide_table = model
+
+    @property
+    def wide_table(self):
+        """The models.WideTableModel set last (None: none)."""
+        return self._wide_table
+
     def table_pass2(self):
         """Histories the second pass took in the most recent QSMD_MODEL_TABLE
-        call (qsmd_get_param "table_pass2_last")."""
+        or QSMD_MODEL_WTABLE call (qsmd_get_param "table_pass2_last")."""
         return self.get_param("table_pass2_last")
 
     def table_memo_hits(self):

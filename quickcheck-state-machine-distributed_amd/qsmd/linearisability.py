@@ -8,7 +8,8 @@
   the closures of a :class:`~qsmd.models.DeviceModel`: the reference's
   Bank / TicketDispenser models, or a :class:`~qsmd.models.TableModel` (any
   finite-state model, tabulated from its closures by
-  ``TableModel.from_closures``); any other closure raises -- there is no CPU
+  ``TableModel.from_closures``; beyond 256 states or 32 symbols a
+  :class:`~qsmd.models.WideTableModel`); any other closure raises -- there is no CPU
   search to fall back to.  Model exceptions propagate as in Haskell
   (:class:`~qsmd.models.ModelError` for ``Map.!``, test/Bank.hs:128).
 * :func:`linearisable_batch` is the throughput entry point.
@@ -24,7 +25,7 @@ from dataclasses import dataclass, field
 import numpy as np
 
 from . import codec, device
-from .models import BY_ID, BY_NAME, DeviceModel, EncodeError, ModelError, TableModel
+from .models import BY_ID, BY_NAME, DeviceModel, EncodeError, ModelError, TableModel, WideTableModel
 
 __all__ = ["linearisable", "linearisable_batch", "trace", "wellformed", "replay_witness",
            "CheckResult", "NotSequential", "BudgetExceeded", "wellformed_batch"]
@@ -40,6 +41,7 @@ def _device_model(transition, postcondition) -> DeviceModel:
             return m
     # a TableModel's closures are bound methods (a new object at every
     # attribute access, so `is` never matches): found through their __self__
+    # (a WideTableModel is a TableModel: the owner's model_id tells them apart)
     owner = getattr(transition, "__self__", None)
     if (isinstance(owner, TableModel) and getattr(postcondition, "__self__", None) is owner
             and getattr(transition, "__func__", None) is TableModel.transition
@@ -48,7 +50,8 @@ def _device_model(transition, postcondition) -> DeviceModel:
     raise NotImplementedError(
         "no device model for these closures: pass the closures of the reference's Bank "
         "(test/Bank.hs) or TicketDispenser (test/TicketDispenser.hs) models, or tabulate a "
-        "finite-state model with qsmd.models.TableModel.from_closures and pass its "
+        "finite-state model with qsmd.models.TableModel.from_closures (WideTableModel beyond "
+        "256 states or 32 symbols) and pass its "
         ".transition / .postcondition")
 
 
@@ -95,7 +98,10 @@ def linearisable_batch(model, histories, model0=None, *, max_nodes=0, witness=Fa
     accounts0 = m.new_account_map(model0)
     packed = m.pack_model0(model0, accounts0)
     ctx = ctx or device.default_context()
-    if isinstance(m, TableModel) and ctx.table is not m:
+    if isinstance(m, WideTableModel):
+        if ctx.wide_table is not m:
+            ctx.set_wide_table(m)
+    elif isinstance(m, TableModel) and ctx.table is not m:
         ctx.set_table(m)
     saved = None
     if table_memo is not None:

@@ -347,16 +347,33 @@ class TableModel(DeviceModel):
 
     name = "table"
     model_id = MODEL_TABLE
+    # the limits and the table formats (WideTableModel widens them)
+    MAX_STATES = TABLE_MAX_STATES
+    MAX_SYMBOLS = TABLE_MAX_SYMBOLS
+    STATE_DTYPE = "uint8"
+
+    @staticmethod
+    def _post_shape(ns, ni, nr):
+        return (ns, ni)
+
+    @staticmethod
+    def _post_entry(bits, nr):
+        """A postcondition bitset (a Python int, bit r = response r) as a table entry."""
+        return bits
+
+    @staticmethod
+    def _post_bit(entry, r):
+        return (int(entry) >> r) & 1
 
     def __init__(self, states, invs, resps, on_inv, on_resp, post, post_err=None, init_state=0):
         import numpy as np
         self.states, self.invs, self.resps = list(states), list(invs), list(resps)
         ns, ni, nr = len(self.states), len(self.invs), len(self.resps)
-        if not 1 <= ns <= TABLE_MAX_STATES:
-            raise EncodeError(f"{ns} states: a table model has 1..{TABLE_MAX_STATES}")
-        if not 1 <= ni <= TABLE_MAX_SYMBOLS or not 1 <= nr <= TABLE_MAX_SYMBOLS:
-            raise EncodeError(f"{ni} invocation / {nr} response symbols: a table model has "
-                              f"1..{TABLE_MAX_SYMBOLS} of each")
+        if not 1 <= ns <= self.MAX_STATES:
+            raise EncodeError(f"{ns} states: a {self.name} model has 1..{self.MAX_STATES}")
+        if not 1 <= ni <= self.MAX_SYMBOLS or not 1 <= nr <= self.MAX_SYMBOLS:
+            raise EncodeError(f"{ni} invocation / {nr} response symbols: a {self.name} model has "
+                              f"1..{self.MAX_SYMBOLS} of each")
         self.state_index = {v: k for k, v in enumerate(self.states)}
         self.inv_index = {v: k for k, v in enumerate(self.invs)}
         self.resp_index = {v: k for k, v in enumerate(self.resps)}
@@ -371,10 +388,11 @@ class TableModel(DeviceModel):
                 raise EncodeError(f"{what}: entry out of range")
             return np.ascontiguousarray(arr.astype(dtype))
 
-        self.on_inv = table(on_inv, (ns, ni), np.uint8, "on_inv")
-        self.on_resp = table(on_resp, (ns, nr), np.uint8, "on_resp")
-        self.post = table(post, (ns, ni), np.uint32, "post")
-        self.post_err = None if post_err is None else table(post_err, (ns, ni), np.uint32, "post_err")
+        sdt, pshape = np.dtype(self.STATE_DTYPE).type, self._post_shape(ns, ni, nr)
+        self.on_inv = table(on_inv, (ns, ni), sdt, "on_inv")
+        self.on_resp = table(on_resp, (ns, nr), sdt, "on_resp")
+        self.post = table(post, pshape, np.uint32, "post")
+        self.post_err = None if post_err is None else table(post_err, pshape, np.uint32, "post_err")
         if self.on_inv.max() >= ns or self.on_resp.max() >= ns:
             raise EncodeError("on_inv / on_resp: entry >= n_states")
         if not 0 <= int(init_state) < ns:
@@ -389,10 +407,11 @@ class TableModel(DeviceModel):
         every ``("L", inv)`` in ``invs`` order and then every ``("R", resp)``
         in ``resps`` order, so state 0 is ``init_model`` and the numbering is
         reproducible.  A ``postcondition`` that raises ``raises`` becomes a
-        post_err bit.  :class:`EncodeError` past 256 states or 32 symbols."""
+        post_err bit.  :class:`EncodeError` past the class's limits (256
+        states and 32 symbols; :class:`WideTableModel`: 65,536 and 256)."""
         invs, resps = list(invs), list(resps)
-        if len(invs) > TABLE_MAX_SYMBOLS or len(resps) > TABLE_MAX_SYMBOLS:
-            raise EncodeError(f"{len(invs)} invocation / {len(resps)} response symbols > {TABLE_MAX_SYMBOLS}")
+        if len(invs) > cls.MAX_SYMBOLS or len(resps) > cls.MAX_SYMBOLS:
+            raise EncodeError(f"{len(invs)} invocation / {len(resps)} response symbols > {cls.MAX_SYMBOLS}")
         states, index = [init_model], {init_model: 0}
         on_inv, on_resp = [], []
         k = 0
@@ -404,8 +423,8 @@ class TableModel(DeviceModel):
                 for ev in evs:
                     t = transition(s, ev)
                     if t not in index:
-                        if len(states) >= TABLE_MAX_STATES:
-                            raise EncodeError(f"more than {TABLE_MAX_STATES} reachable states")
+                        if len(states) >= cls.MAX_STATES:
+                            raise EncodeError(f"more than {cls.MAX_STATES} reachable states")
                         index[t] = len(states)
                         states.append(t)
                     row.append(index[t])
@@ -425,7 +444,10 @@ class TableModel(DeviceModel):
                     except raises:
                         err[si][ii] |= 1 << ri
                         any_err = True
-        return cls(states, invs, resps, on_inv, on_resp, post, err if any_err else None, 0)
+        nr = len(resps)
+        post = [[cls._post_entry(b, nr) for b in row] for row in post]
+        err = [[cls._post_entry(b, nr) for b in row] for row in err] if any_err else None
+        return cls(states, invs, resps, on_inv, on_resp, post, err, 0)
 
     @property
     def init_model(self):
@@ -447,10 +469,10 @@ class TableModel(DeviceModel):
 
     def postcondition(self, m, inv, resp):
         s, i, r = self._state(m), self.encode_inv(inv, None)[0], self.encode_resp(resp)[0]
-        if self.post_err is not None and (int(self.post_err[s, i]) >> r) & 1:
+        if self.post_err is not None and self._post_bit(self.post_err[s, i], r):
             raise ModelError(f"postcondition raises: {self.show_model(m)}, {self.show_inv(inv)}, "
                              f"{self.show_resp(resp)}")
-        return bool((int(self.post[s, i]) >> r) & 1)
+        return bool(self._post_bit(self.post[s, i], r))
 
     def encode_inv(self, inv, accounts):
         try:
@@ -476,11 +498,51 @@ class TableModel(DeviceModel):
         return ctypes.c_uint32(self._state(model0))
 
     def c_struct(self):
-        """The ``qsmd_table_model`` of this model (pointers into its arrays,
-        which live as long as the model)."""
+        """The ``qsmd_table_model`` (``qsmd_wtable_model``) of this model
+        (pointers into its arrays, which live as long as the model)."""
         return TableModelStruct(len(self.states), len(self.invs), len(self.resps), self.init_state,
                                 self.on_inv.ctypes.data, self.on_resp.ctypes.data, self.post.ctypes.data,
                                 None if self.post_err is None else self.post_err.ctypes.data)
+
+
+# ---------------------------------------------------------------------------
+# Wide table-driven models (include/qsmd.h QSMD_MODEL_WTABLE)
+# ---------------------------------------------------------------------------
+
+MODEL_WTABLE = 4
+WTABLE_MAX_STATES = 65536
+WTABLE_MAX_SYMBOLS = 256
+
+
+class WideTableModel(TableModel):
+    """A :class:`TableModel` beyond its limits: up to 65,536 states and 256
+    invocation / 256 response symbols (``QSMD_MODEL_WTABLE``; the kernel reads
+    the tables from device memory, so a model that fits a
+    :class:`TableModel` is checked faster as one).  ``on_inv`` / ``on_resp``
+    are ``uint16``; ``post`` / ``post_err`` have shape ``(n_states, n_inv,
+    post_words)`` with ``post_words = ceil(n_resp / 32)``, response ``r`` being
+    bit ``r & 31`` of word ``r >> 5``.  Everything else -- the step, the
+    methods, :meth:`from_closures` and its numbering -- is
+    :class:`TableModel`'s.  The device copy is held to
+    ``QSMD_WTABLE_MAX_BYTES`` (64 MiB) by ``Context.set_wide_table``."""
+
+    name = "wtable"
+    model_id = MODEL_WTABLE
+    MAX_STATES = WTABLE_MAX_STATES
+    MAX_SYMBOLS = WTABLE_MAX_SYMBOLS
+    STATE_DTYPE = "uint16"
+
+    @staticmethod
+    def _post_shape(ns, ni, nr):
+        return (ns, ni, (nr + 31) // 32)
+
+    @staticmethod
+    def _post_entry(bits, nr):
+        return [(bits >> (32 * k)) & 0xFFFFFFFF for k in range((nr + 31) // 32)]
+
+    @staticmethod
+    def _post_bit(entry, r):
+        return (int(entry[r >> 5]) >> (r & 31)) & 1
 
 
 TICKET = TicketDispenser()

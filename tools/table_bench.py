@@ -10,7 +10,15 @@ One JSON line per budget and memo size ("table_memo", --memo: entries per
 lane slot of pass 2's state memo, 0 = off), the sizes crossed with every
 budget.  --rounds R repeats the whole cross R times (interleaved).
 
+--wide both runs every configuration as QSMD_MODEL_TABLE and then as
+QSMD_MODEL_WTABLE (csrc/wtable.hip: the tables in device memory) on the same
+batch with only hdr.model_id changed, the two interleaved: what a model that
+fits the narrow table pays on the wide path.  --wide 1 runs the wide path
+alone.  --model kv is the 5-key, 4-value store of tests/wtablegen.py (1,024
+states, 105 invocations), which only the wide path holds.
+
     python tools/table_bench.py [--budgets default,0] [--memo 0,64,256,1024,4096] [--distinct 65536] [--n 1048576]
+                                [--wide 0|1|both] [--model register|kv]
 """
 
 import argparse
@@ -28,7 +36,7 @@ for p in ("quickcheck-state-machine-distributed_amd", "oracle", "tests"):
 
 import tablegen as tg  # noqa: E402
 from qsmd import codec, device  # noqa: E402
-from qsmd.models import TableModel  # noqa: E402
+from qsmd.models import TableModel, WideTableModel  # noqa: E402
 
 
 def main():
@@ -41,12 +49,19 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--calls", type=int, default=20)
     ap.add_argument("--max-nodes", type=int, default=tg.MAX_NODES)
+    ap.add_argument("--wide", default="0", choices=["0", "1", "both"])
+    ap.add_argument("--model", default="register", choices=["register", "kv"])
     args = ap.parse_args()
     import torch
 
-    model = tg.REGISTER
-    m = TableModel.from_closures(model["transition"], model["postcondition"], model["init"], model["invs"],
-                                 model["resps"])
+    if args.model == "kv":
+        import wtablegen as wg
+        model, args.wide = wg.KV, "1"
+    else:
+        model = tg.REGISTER
+    ids = {"0": [3], "1": [4], "both": [3, 4]}[args.wide]
+    closures = (model["transition"], model["postcondition"], model["init"], model["invs"], model["resps"])
+    m = (TableModel if 3 in ids else WideTableModel).from_closures(*closures)
     rng = random.Random("table_bench")
     hists = [tg.gen_history(model, rng, 4, 16, 0.03) for _ in range(args.distinct)]
     batch = codec.encode(m, hists)
@@ -59,17 +74,25 @@ def main():
     ev = np.tile(batch.events, reps)
 
     dev = torch.device("cuda:0")
-    d_hdr = torch.from_numpy(hdr.view(np.uint8)).to(dev)
+    d_hdrs = {}
+    for mid in ids:                         # the same batch, only hdr.model_id changed
+        hdr["model_id"] = mid
+        d_hdrs[mid] = torch.from_numpy(hdr.view(np.uint8).copy()).to(dev)
     d_ev = torch.from_numpy(ev.view(np.uint8)).to(dev)
     d_st = torch.empty(n, dtype=torch.uint8, device=dev)
     d_nd = torch.empty(n, dtype=torch.int64, device=dev)
     d_tot = torch.zeros(8, dtype=torch.int64, device=dev)
     stream = torch.cuda.current_stream().cuda_stream
     ctx = device.Context(0, time_limit_ms=60000)
-    ctx.set_table(m)
+    if 3 in ids:
+        ctx.set_table(m)
+    if 4 in ids:
+        ctx.set_wide_table(m if isinstance(m, WideTableModel) else WideTableModel.from_closures(*closures))
     default = ctx.get_param("table_budget")
-    cross = [(b, int(e)) for _ in range(args.rounds) for b in args.budgets.split(",") for e in args.memo.split(",")]
-    for b, entries in cross:
+    cross = [(b, int(e), mid) for _ in range(args.rounds) for b in args.budgets.split(",")
+             for e in args.memo.split(",") for mid in ids]
+    for b, entries, mid in cross:
+        d_hdr = d_hdrs[mid]
         budget = default if b == "default" else int(b)
         ctx.set_param("table_budget", budget)
         ctx.set_param("table_memo", entries)
@@ -77,7 +100,7 @@ def main():
         for k in range(args.warmup + args.calls):
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             e0.record()
-            ctx.check_device(3, d_hdr.data_ptr(), n, d_ev.data_ptr(), len(ev), d_st.data_ptr(), d_nd.data_ptr(),
+            ctx.check_device(mid, d_hdr.data_ptr(), n, d_ev.data_ptr(), len(ev), d_st.data_ptr(), d_nd.data_ptr(),
                              None, d_tot.data_ptr(), max_nodes=args.max_nodes, stream=stream)
             e1.record()
             torch.cuda.synchronize()
@@ -86,7 +109,8 @@ def main():
         tot = d_tot.cpu().numpy()
         med = statistics.median(ms)
         print(json.dumps({
-            "workload": f"register 4x16 p_bug 0.03, {args.distinct} distinct tiled to {n}, device-resident",
+            "model_id": mid,
+            "workload": f"{args.model} 4x16 p_bug 0.03, {args.distinct} distinct tiled to {n}, device-resident",
             "table_budget": budget, "is_default": budget == default, "table_memo": entries,
             "table_memo_hits": ctx.table_memo_hits(), "calls": args.calls,
             "ms_per_call_median": round(med, 4), "ms_min": round(min(ms), 4), "ms_max": round(max(ms), 4),
