@@ -12,6 +12,7 @@
 
 #include <algorithm>
 #include <chrono>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -23,6 +24,7 @@
 
 #include "internal.h"
 #include "qsmd_gen.h"
+#include "tgen.h"
 
 #include "qsmd.h"
 
@@ -1453,6 +1455,72 @@ int qsmd_gen_batch_device(qsmd_ctx* c, const qsmd_gen_params* p, uint64_t first,
     HIP_TRY(c, hipSetDevice(c->device), "hipSetDevice");
     HIP_TRY(c, launch_gen(*p, first, n_hist, ev_base, hdr_dev, events_dev, bug_dev,
                           stream ? static_cast<hipStream_t>(stream) : ctx_stream(c)), "gen launch");
+    return QSMD_OK;
+}
+
+// The table models' generator (csrc/tgen.hip).  One of the context's ordered
+// calls: it reads the context's table, which qsmd_table_set / qsmd_wtable_set
+// free once the last call is done.
+int qsmd_gen_table_batch_device(qsmd_ctx* c, const qsmd_gen_table_params* p, uint64_t first, uint64_t n_hist,
+                                uint32_t ev_base, qsmd_hdr* hdr_dev, qsmd_event* events_dev, uint8_t* bug_dev,
+                                void* stream) {
+    if (!c) return QSMD_ERR_ARG;
+    std::lock_guard<std::mutex> g(c->mu);
+    // the parameter checks of qsmd_gen_table_batch (csrc/gen/tgen.cpp)
+    if (!p || (n_hist && (!hdr_dev || !events_dev))) return fail(c, QSMD_ERR_ARG, "null params/buffers");
+    if (p->model_id != QSMD_MODEL_TABLE && p->model_id != QSMD_MODEL_WTABLE) return fail(c, QSMD_ERR_ARG, "model_id");
+    const bool wide = p->model_id == QSMD_MODEL_WTABLE;
+    if (wide ? !c->wtab_blob : !c->tab_blob)
+        return fail(c, QSMD_ERR_ARG, "no table set (qsmd_table_set / qsmd_wtable_set)");
+    if (p->n_clients < 1 || p->n_clients > 32) return fail(c, QSMD_ERR_ARG, "n_clients outside 1..32");
+    if (p->n_ops < 1 || 2 * p->n_ops > QSMD_MAX_EVENTS) return fail(c, QSMD_ERR_ARG, "n_ops outside 1..64");
+    if (p->lin_policy > 1 || p->pid_mode > 1) return fail(c, QSMD_ERR_ARG, "lin_policy / pid_mode");
+    if (!(p->p_bug >= 0.0 && p->p_bug <= 1.0)) return fail(c, QSMD_ERR_ARG, "p_bug outside [0, 1]");
+    if ((uint64_t)ev_base + n_hist * 2ull * p->n_ops > 0xFFFFFFFFull || n_hist > 0xFFFFFFFFull)
+        return fail(c, QSMD_ERR_ARG, "ev_off beyond u32");
+    TGenArgs a{};
+    const uint32_t n_inv = wide ? c->wtab.n_inv : c->tab.n_inv;
+    uint64_t w_all = 0;
+    a.w_unit = 1u;
+    for (uint32_t i = 0; i < n_inv; ++i) {
+        const uint32_t w = a.weight[i] = p->inv_weight ? p->inv_weight[i] : 1u;
+        w_all += w;
+        if (w > 1u) a.w_unit = 0u;
+        if (w && i < 32u) a.w_mask |= 1u << i;
+    }
+    if (w_all == 0 || w_all > 0xFFFFFFFFull) return fail(c, QSMD_ERR_ARG, "inv_weight: all zero or a sum past 2^32 - 1");
+    if (n_hist == 0) return QSMD_OK;
+    if (wide) a.wt = c->wtab; else a.t = c->tab;
+    a.state0 = wide ? c->wtab_init : c->tab_init;
+    a.model_id = p->model_id;
+    a.n_clients = p->n_clients;
+    a.n_ops = p->n_ops;
+    a.prefix = std::min(p->prefix_ops, p->n_ops);
+    a.in_window = p->lin_policy == QSMD_GEN_LIN_IN_WINDOW;
+    a.shared = p->pid_mode == QSMD_GEN_PID_SHARED;
+    a.overlap = p->overlap ? p->overlap : p->n_clients;
+    a.w_all = (uint32_t)w_all;
+    // unit() < p_bug  <=>  (next() >> 11) * 2^-53 < p_bug  <=>  (next() >> 11) < ceil(p_bug * 2^53):
+    // the scaling is exact, so the kernel compares integers
+    a.bug_draw = p->p_bug > 0.0;
+    a.bug_below = (uint64_t)std::ceil(std::ldexp(p->p_bug, 53));
+    a.seed = p->seed;
+    a.first = first;
+    a.n_hist = n_hist;
+    a.ev_base = ev_base;
+    a.hdr = hdr_dev;
+    a.events = events_dev;
+    a.bug = bug_dev;
+    HIP_TRY(c, hipSetDevice(c->device), "hipSetDevice");
+    hipStream_t s = stream ? static_cast<hipStream_t>(stream) : ctx_stream(c);
+    if (!s) return fail(c, QSMD_ERR_DEVICE, "hipStreamCreate");
+    HIP_TRY(c, order_after_previous(c, s), "order after the previous call");
+    HIP_TRY(c, launch_tgen(a, (uint32_t)c->n_cu, s), "table gen launch");
+    const bool own = s == c->stream;
+    if (!own) HIP_TRY(c, hipEventRecord(c->done_ev, s), "hipEventRecord");
+    c->done_last = !own;
+    c->last_stream = s;
+    c->in_flight = true;
     return QSMD_OK;
 }
 

@@ -69,6 +69,7 @@ EXPORTS = {
     "qsmd_wellformed_batch": (_I, [_P, _P, _U64, _P, _U64, _P, _U32, _P]),
     "qsmd_wellformed_batch_device": (_I, [_P, _P, _U64, _P, _U64, _P, _U32, _P, _P]),
     "qsmd_gen_batch_device": (_I, [_P, _P, _U64, _U64, _U32, _P, _P, _P, _P]),   # include/qsmd_gen.h
+    "qsmd_gen_table_batch_device": (_I, [_P, _P, _U64, _U64, _U32, _P, _P, _P, _P]),
     "qsmd_check_batch": (_I, [_P, _U32, _P, _U64, _P, _U64, _P, _U32, _U64, _P, _P, _P, _P]),
     "qsmd_check_batch_device": (_I, [_P, _U32, _P, _U64, _P, _U64, _P, _U32, _U64, _P, _P, _P, _P, _P]),
     "qsmd_last_kernel_ms": (_I, [_P, ctypes.POINTER(ctypes.c_float)]),
@@ -353,6 +354,22 @@ class Context:
         rc = self._lib.qsmd_gen_batch_device(self._h, ctypes.byref(params), first, n_hist, ev_base, hdr_ptr,
                                              events_ptr, bug_ptr, stream)
         self._check(rc, "qsmd_gen_batch_device")
+
+    def gen_table_device(self, params, first, n_hist, hdr_ptr, events_ptr, bug_ptr=None, ev_base=0, stream=None,
+                         wide=False):
+        """On-device generation from the context's table (include/qsmd_gen.h
+        qsmd_gen_table_batch_device): the qsmd.gen.generate_table stream
+        [first, first + n_hist), byte-identical to the host generator, into
+        device buffers (async).  ``params``: a gen.TableGenParams; ``wide``:
+        generate from the wide table (set_wide_table) instead of the narrow
+        one (set_table) -- ``params.model_id`` is set accordingly."""
+        params.model_id = 4 if wide else 3
+        held, w = self._wide_table if wide else self._table, getattr(params, "_weights", None)
+        if held is not None and w is not None and len(w) != len(held.invs):
+            raise ValueError(f"{len(w)} weights for a table of {len(held.invs)} invocation symbols")
+        rc = self._lib.qsmd_gen_table_batch_device(self._h, ctypes.byref(params), first, n_hist, ev_base, hdr_ptr,
+                                                   events_ptr, bug_ptr, stream)
+        self._check(rc, "qsmd_gen_table_batch_device")
 
     def probe(self):
         """Routing of the most recent check call (qsmd_probe_read): histories

@@ -33,6 +33,15 @@ class GenParams(ctypes.Structure):
                 ("p_bug", ctypes.c_double), ("seed", ctypes.c_uint64)]
 
 
+class TableGenParams(ctypes.Structure):
+    """``qsmd_gen_table_params`` (include/qsmd_gen.h)."""
+    _fields_ = [("model_id", ctypes.c_uint32), ("n_clients", ctypes.c_uint32),
+                ("n_ops", ctypes.c_uint32), ("prefix_ops", ctypes.c_uint32),
+                ("lin_policy", ctypes.c_uint32), ("pid_mode", ctypes.c_uint32),
+                ("overlap", ctypes.c_uint32), ("p_bug", ctypes.c_double),
+                ("seed", ctypes.c_uint64), ("inv_weight", ctypes.c_void_p)]
+
+
 _lib = None
 
 
@@ -46,6 +55,11 @@ def _load():
         L.qsmd_gen_batch.argtypes = [ctypes.POINTER(GenParams), ctypes.c_uint64, ctypes.c_uint64,
                                      ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p,
                                      ctypes.c_void_p, ctypes.c_int]
+        L.qsmd_gen_table_batch.restype = ctypes.c_int
+        L.qsmd_gen_table_batch.argtypes = [ctypes.POINTER(TableGenParams), ctypes.c_void_p,
+                                           ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint32,
+                                           ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                           ctypes.c_int]
         _lib = L
     return _lib
 
@@ -90,6 +104,47 @@ def generate(p, first, n_hist, threads=8, ev_base=0):
     if rc != 0:
         raise ValueError(f"qsmd_gen_batch rejected the parameters ({rc})")
     return hdr, events, bug
+
+
+def table_params(inv_weight=None, **kw):
+    """A TableGenParams.  ``inv_weight``: one weight per invocation symbol of
+    the model the parameters will be used with (None = every weight 1); the
+    array is kept alive by the returned structure.  ``model_id`` is filled in
+    by generate_table / Context.gen_table_device from the model."""
+    p = TableGenParams()
+    for k, v in kw.items():
+        setattr(p, k, v)
+    if inv_weight is not None:
+        w = np.ascontiguousarray(inv_weight, dtype=np.uint32)
+        p._weights = w
+        p.inv_weight = w.ctypes.data
+    return p
+
+
+def _table_weights_fit(p, model):
+    w = getattr(p, "_weights", None)
+    if w is not None and len(w) != len(model.invs):
+        raise ValueError(f"{len(w)} weights for a model of {len(model.invs)} invocation symbols")
+
+
+def generate_table(p, model, first, n_hist, threads=8, ev_base=0):
+    """qsmd_gen_table_batch: (hdr, events, flags) numpy arrays for histories
+    [first, first + n_hist) of the stream ``p`` defines over ``model`` (a
+    models.TableModel or models.WideTableModel; ``p.model_id`` is set from its
+    class).  flags: bit 0 an injected bug, bit 1 a stuck step."""
+    lib = _load()
+    _table_weights_fit(p, model)
+    p.model_id = model.model_id
+    per = 2 * p.n_ops
+    hdr = np.zeros(n_hist, dtype=codec.HDR_DTYPE)
+    events = np.zeros(n_hist * per, dtype=codec.EV_DTYPE)
+    flags = np.zeros(n_hist, dtype=np.uint8)
+    st = model.c_struct()
+    rc = lib.qsmd_gen_table_batch(ctypes.byref(p), ctypes.addressof(st), first, n_hist, ev_base,
+                                  hdr.ctypes.data, events.ctypes.data, flags.ctypes.data, threads)
+    if rc != 0:
+        raise ValueError(f"qsmd_gen_table_batch rejected the parameters ({rc})")
+    return hdr, events, flags
 
 
 def adversarial_ticket(n_clients=8, n_ops=64, bug=True):

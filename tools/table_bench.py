@@ -17,8 +17,17 @@ fits the narrow table pays on the wide path.  --wide 1 runs the wide path
 alone.  --model kv is the 5-key, 4-value store of tests/wtablegen.py (1,024
 states, 105 invocations), which only the wide path holds.
 
+--generated: the batch is --n DISTINCT histories generated on the device
+(csrc/tgen.hip, Context.gen_table_device) from (seed, index) over the same
+tables: 4 clients x 16 operations, executed at the invocation as
+tests/tablegen.py's are, one response bug in 39 % of the histories (its 3 %
+per operation over 16).  No tiling and no host-to-device copy.  With an
+explicit --distinct D the first D generated histories are tiled to --n on the
+device instead, which isolates what tiling does to the measurement.  Without
+the flag the tool does exactly what it did before it had one.
+
     python tools/table_bench.py [--budgets default,0] [--memo 0,64,256,1024,4096] [--distinct 65536] [--n 1048576]
-                                [--wide 0|1|both] [--model register|kv]
+                                [--wide 0|1|both] [--model register|kv] [--generated] [--seed S]
 """
 
 import argparse
@@ -35,7 +44,7 @@ for p in ("quickcheck-state-machine-distributed_amd", "oracle", "tests"):
     sys.path.insert(0, os.path.join(ROOT, p))
 
 import tablegen as tg  # noqa: E402
-from qsmd import codec, device  # noqa: E402
+from qsmd import codec, device, gen  # noqa: E402
 from qsmd.models import TableModel, WideTableModel  # noqa: E402
 
 
@@ -44,14 +53,19 @@ def main():
     ap.add_argument("--budgets", default="default,0")
     ap.add_argument("--memo", default="0")
     ap.add_argument("--rounds", type=int, default=1)
-    ap.add_argument("--distinct", type=int, default=65536)
+    ap.add_argument("--distinct", type=int, default=None)
     ap.add_argument("--n", type=int, default=1 << 20)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--calls", type=int, default=20)
     ap.add_argument("--max-nodes", type=int, default=tg.MAX_NODES)
     ap.add_argument("--wide", default="0", choices=["0", "1", "both"])
     ap.add_argument("--model", default="register", choices=["register", "kv"])
+    ap.add_argument("--generated", action="store_true")
+    ap.add_argument("--seed", type=int, default=0x7AB1E)
     args = ap.parse_args()
+    tiled = args.distinct is not None or not args.generated
+    if args.distinct is None:
+        args.distinct = 65536 if tiled else args.n
     import torch
 
     if args.model == "kv":
@@ -62,32 +76,56 @@ def main():
     ids = {"0": [3], "1": [4], "both": [3, 4]}[args.wide]
     closures = (model["transition"], model["postcondition"], model["init"], model["invs"], model["resps"])
     m = (TableModel if 3 in ids else WideTableModel).from_closures(*closures)
-    rng = random.Random("table_bench")
-    hists = [tg.gen_history(model, rng, 4, 16, 0.03) for _ in range(args.distinct)]
-    batch = codec.encode(m, hists)
-    reps = (args.n + args.distinct - 1) // args.distinct
-    n = reps * args.distinct
-    per = len(batch.events)
-    hdr = np.tile(batch.hdr, reps)
-    hdr["ev_off"] = (hdr["ev_off"].astype(np.int64) + np.repeat(np.arange(reps, dtype=np.int64) * per,
-                                                                 args.distinct)).astype(np.uint32)
-    ev = np.tile(batch.events, reps)
-
     dev = torch.device("cuda:0")
-    d_hdrs = {}
-    for mid in ids:                         # the same batch, only hdr.model_id changed
-        hdr["model_id"] = mid
-        d_hdrs[mid] = torch.from_numpy(hdr.view(np.uint8).copy()).to(dev)
-    d_ev = torch.from_numpy(ev.view(np.uint8)).to(dev)
-    d_st = torch.empty(n, dtype=torch.uint8, device=dev)
-    d_nd = torch.empty(n, dtype=torch.int64, device=dev)
-    d_tot = torch.zeros(8, dtype=torch.int64, device=dev)
     stream = torch.cuda.current_stream().cuda_stream
     ctx = device.Context(0, time_limit_ms=60000)
     if 3 in ids:
         ctx.set_table(m)
     if 4 in ids:
         ctx.set_wide_table(m if isinstance(m, WideTableModel) else WideTableModel.from_closures(*closures))
+    reps = (args.n + args.distinct - 1) // args.distinct
+    n = reps * args.distinct
+    d_hdrs = {}
+    if args.generated:
+        per = 32
+        gp = gen.table_params(n_clients=4, n_ops=16, prefix_ops=0, lin_policy=gen.LIN_AT_INVOKE,
+                              pid_mode=gen.PID_PER_CLIENT, p_bug=0.39, seed=args.seed)
+        d_ev = torch.empty(n * per * 8, dtype=torch.uint8, device=dev)
+        for mid in ids:                     # the same stream from either table: only hdr.model_id differs
+            h = torch.empty(n * 16, dtype=torch.uint8, device=dev)
+            ctx.gen_table_device(gp, 0, args.distinct, h.data_ptr(), d_ev.data_ptr(), None, stream=stream,
+                                 wide=mid == 4)
+            torch.cuda.synchronize()
+            if reps > 1:                    # tile on the device: ev_off moves on by one tile's events
+                first = h[:args.distinct * 16].view(torch.int32).view(args.distinct, 4)
+                tiles = first.repeat(reps, 1)
+                tiles[:, 0] += torch.arange(reps, device=dev, dtype=torch.int32).repeat_interleave(
+                    args.distinct) * (args.distinct * per)
+                h = tiles.view(torch.uint8).reshape(-1)
+            d_hdrs[mid] = h
+        if reps > 1:
+            d_ev = d_ev[:args.distinct * per * 8].repeat(reps)
+        n_events = n * per
+        what = (f"{args.model} 4x16 generated on the device (seed {args.seed:#x}, p_bug 0.39), " +
+                (f"{args.distinct} distinct tiled to {n}" if reps > 1 else f"{n} distinct"))
+    else:
+        rng = random.Random("table_bench")
+        hists = [tg.gen_history(model, rng, 4, 16, 0.03) for _ in range(args.distinct)]
+        batch = codec.encode(m, hists)
+        per = len(batch.events)
+        hdr = np.tile(batch.hdr, reps)
+        hdr["ev_off"] = (hdr["ev_off"].astype(np.int64) + np.repeat(np.arange(reps, dtype=np.int64) * per,
+                                                                     args.distinct)).astype(np.uint32)
+        ev = np.tile(batch.events, reps)
+        for mid in ids:                     # the same batch, only hdr.model_id changed
+            hdr["model_id"] = mid
+            d_hdrs[mid] = torch.from_numpy(hdr.view(np.uint8).copy()).to(dev)
+        d_ev = torch.from_numpy(ev.view(np.uint8)).to(dev)
+        n_events = len(ev)
+        what = f"{args.model} 4x16 p_bug 0.03, {args.distinct} distinct tiled to {n}, device-resident"
+    d_st = torch.empty(n, dtype=torch.uint8, device=dev)
+    d_nd = torch.empty(n, dtype=torch.int64, device=dev)
+    d_tot = torch.zeros(8, dtype=torch.int64, device=dev)
     default = ctx.get_param("table_budget")
     cross = [(b, int(e), mid) for _ in range(args.rounds) for b in args.budgets.split(",")
              for e in args.memo.split(",") for mid in ids]
@@ -100,7 +138,7 @@ def main():
         for k in range(args.warmup + args.calls):
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             e0.record()
-            ctx.check_device(mid, d_hdr.data_ptr(), n, d_ev.data_ptr(), len(ev), d_st.data_ptr(), d_nd.data_ptr(),
+            ctx.check_device(mid, d_hdr.data_ptr(), n, d_ev.data_ptr(), n_events, d_st.data_ptr(), d_nd.data_ptr(),
                              None, d_tot.data_ptr(), max_nodes=args.max_nodes, stream=stream)
             e1.record()
             torch.cuda.synchronize()
@@ -110,7 +148,7 @@ def main():
         med = statistics.median(ms)
         print(json.dumps({
             "model_id": mid,
-            "workload": f"{args.model} 4x16 p_bug 0.03, {args.distinct} distinct tiled to {n}, device-resident",
+            "workload": what,
             "table_budget": budget, "is_default": budget == default, "table_memo": entries,
             "table_memo_hits": ctx.table_memo_hits(), "calls": args.calls,
             "ms_per_call_median": round(med, 4), "ms_min": round(min(ms), 4), "ms_max": round(max(ms), 4),
