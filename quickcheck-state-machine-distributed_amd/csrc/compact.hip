@@ -38,20 +38,22 @@
 namespace qsmd {
 
 // Run one lane's search to its end (status), with the early-exit and time
-// limit checks every 1024 iterations.
-template <class DFS>
+// limit checks every 1024 iterations.  LOW4: no searching lane of the
+// wavefront has a pid above 3 (LaneDFS::same_pid without its third slice).
+template <bool LOW4, class DFS>
 __device__ __forceinline__ int run_search(DFS& dfs, const SearchArgs& a, const uint32_t* evc,
                                           int32_t (*s_bal)[C_LANES], int lane, uint64_t limit, uint32_t h,
                                           uint64_t t0) {
     int status = -1;
     while (true) {
-        // 1024 steps between the checks (the inner loop's only test is the
-        // step's one exit, see LaneDFS::step)
-        // (a wavefront-uniform counter: the loop runs while any lane
-        // searches, the finished lanes masked off)
-        for (uint32_t k = 0; k < 1024u; ++k) {
-            if (status < 0) status = dfs.template step<C_LANES>(a, evc, s_bal, lane, limit);
-            if (__ballot(status < 0) == 0ull) break;
+        // 1024 steps between the checks.  A lane leaves the loop with its
+        // status, so the loop's own exec mask is the set of searching lanes:
+        // no test of the status per step, no ballot (the count is the same
+        // in every lane still searching)
+        uint32_t k = 0;
+        while (status < 0) {
+            status = dfs.template step<C_LANES, LOW4>(a, evc, s_bal, lane, limit);
+            if (++k == 1024u) break;
         }
         if (status >= 0) break;
         if (beyond_first_fail(a, h)) {
@@ -155,8 +157,16 @@ __global__ __launch_bounds__(C_LANES, G::EV == 32 ? 4 : 2) void compact_search(S
         const bool live = status != -2;     // (-2: no history here, or handed to the next stage)
         const bool search = status == -1;
         const uint32_t n_ev = H.n_ev;
-        // the general path (pid masks): finish_lane does not pair (lane.h)
-        if (search) status = run_search(dfs, a, &s_ev[0][lane], s_bal, lane, limit, h, t0);
+        // the general path (pid masks): finish_lane does not pair (lane.h).
+        // One choice per group (stage 0): when no history to search has a
+        // pid above 3, the pid compare leaves out its third slice.
+        bool low4 = false;
+        if constexpr (G::EV == 32) low4 = __ballot(search && dfs.P2 != 0u) == 0ull;
+        if (low4) {
+            if (search) status = run_search<true>(dfs, a, &s_ev[0][lane], s_bal, lane, limit, h, t0);
+        } else {
+            if (search) status = run_search<false>(dfs, a, &s_ev[0][lane], s_bal, lane, limit, h, t0);
+        }
         note_failure(a, h, status);
         // over the stage budget (not the caller's): searched again by the heavy stage
         const bool heavy = tiered && status == QSMD_STATUS_BUDGET && dfs.nodes >= limit;

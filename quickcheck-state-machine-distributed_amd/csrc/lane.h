@@ -562,10 +562,14 @@ struct LaneDFS {
     // bits beyond the history are not cleared -- every use ANDs the result
     // with INV or RESP (u32: each slice's bit j sign-extended by one v_bfe_i32,
     // then two 3-input logic ops)
+    // LOW4 (the caller knows every pid of the history is below 4: P2 == 0):
+    // the third slice is left out
+    template <bool LOW4 = false>
     __device__ __forceinline__ M same_pid(uint32_t j) const {
         if constexpr (sizeof(M) == 4) {
             const uint32_t m0 = (uint32_t)__builtin_amdgcn_sbfe((int32_t)P0, j, 1u);
             const uint32_t m1 = (uint32_t)__builtin_amdgcn_sbfe((int32_t)P1, j, 1u);
+            if constexpr (LOW4) return ~((P0 ^ m0) | (P1 ^ m1));
             const uint32_t m2 = (uint32_t)__builtin_amdgcn_sbfe((int32_t)P2, j, 1u);
             return ~((P0 ^ m0) | (P1 ^ m1) | (P2 ^ m2));
         } else {
@@ -599,14 +603,14 @@ struct LaneDFS {
     // a history shared by the wavefront: STRIDE = 1)
     // Undo the last level: restore the parent node's state exactly
     // (remaining events, model); returns the candidate the level went through.
-    template <int STRIDE, bool FOLD = false>
+    template <int STRIDE, bool FOLD = false, bool LOW4 = false>
     __device__ __forceinline__ uint32_t undo(const uint32_t* evc, int32_t (*s_bal)[C_LANES], int lane) {
         --depth;
         const uint32_t st = stk.top();
         stk.pop();
         const uint32_t j = st & JM;
         const uint32_t cj = BANK ? evc[j * STRIDE] : 0u;
-        const M gone = ~rem & same_pid(j);
+        const M gone = ~rem & same_pid<LOW4>(j);
         rem |= m_topbit(gone & INV) | m_topbit(gone & RESP);
         if constexpr (BANK) {
             const uint32_t code = c_code(cj), ia = c_a(cj), ib = c_b(cj);
@@ -652,7 +656,8 @@ struct LaneDFS {
                                : ((!found && depth > 0) ? QSMD_STATUS_LINEARISABLE : QSMD_STATUS_NONLINEARISABLE);
     }
 
-    template <int STRIDE>
+    // LOW4: the history has no pid above 3 (same_pid)
+    template <int STRIDE, bool LOW4 = false>
     __device__ __forceinline__ int step(const SearchArgs& a, const uint32_t* evc,
                                         int32_t (*s_bal)[C_LANES], int lane, uint64_t limit) {
         // one exit at the end (no early returns: the state stays in place
@@ -664,23 +669,23 @@ struct LaneDFS {
         int status = term ? kTerm : -1;    // (the outcome itself: finish())
         if (empty & !term) {
             // ---- backtrack: restore the parent level exactly
-            const uint32_t j = undo<STRIDE>(evc, s_bal, lane);
+            const uint32_t j = undo<STRIDE, false, LOW4>(evc, s_bal, lane);
             cand = cands(rem, INV, RESP) & mask_above(j, (M)0);
             found = 1u;
         }
-        if (cand) status = try_next<STRIDE>(a, evc, s_bal, lane, limit);
+        if (cand) status = try_next<STRIDE, false, LOW4>(a, evc, s_bal, lane, limit);
         return status;
     }
 
     // ---- try the next candidate: straight-line, predicated
-    template <int STRIDE, bool FOLD = false>
+    template <int STRIDE, bool FOLD = false, bool LOW4 = false>
     __device__ __forceinline__ int try_next(const SearchArgs& a, const uint32_t* evc,
                                             int32_t (*s_bal)[C_LANES], int lane, uint64_t limit) {
         const uint32_t j = m_ctz(cand);
         cand &= cand - (M)1;
         last_j = j;
         const uint32_t cj = evc[j * STRIDE];
-        const M pmj = same_pid(j);
+        const M pmj = same_pid<LOW4>(j);
         const M rr = rem & pmj & RESP;
         const bool has = rr != (M)0;           // findResponse => [] : no child
         const uint32_t r = m_ctz(rr | ((M)1 << JM));
