@@ -12,6 +12,7 @@
 
 #include "internal.h"
 #include "models.h"
+#include "scatter_map.h"
 
 namespace qsmd {
 
@@ -299,12 +300,13 @@ __device__ __forceinline__ void stage_lane(const SearchArgs& a, const qsmd_hdr& 
 // with fully coalesced 16-byte loads (a per-lane history walk touches 64
 // cache lines per wave instruction), each event is compressed and written
 // to its history's lane column.
-__device__ __forceinline__ uint32_t magic_div(uint32_t N0) { return (uint32_t)(0xFFFFFFFFull / N0) + 1u; }
+__device__ __forceinline__ uint32_t magic_div(uint32_t N0) { return sm_magic(N0); }
 
-// The block's loads go 4 x 16 B per lane at a time (the stage is bound by
-// VALU issue, not by these round trips: 8 or 16 at a time measured no
-// faster).  A power-of-two length (the common packed batch) maps block event
-// g to its history (= column) by a shift.
+// The block's loads go in steps of 4 x 16 B per lane, two steps at a time
+// where the registers allow (below).  A power-of-two length (the common packed batch) maps block event
+// g to its history (= column) by a shift, and its lanes take the pairs of a
+// step in the order of scatter_map.h (a quad of lanes per history instead of
+// 16 lanes: the stores' bank conflicts 4-way instead of 16-way).
 // DEFER: the words are built without the per-event validity select
 // (compress_deferred); returns the lane's suspicion bits -- 0 when every
 // event it compressed is stored as compress() would store it.
@@ -320,24 +322,28 @@ __device__ __forceinline__ uint32_t stage_packed_body(const SearchArgs& a, uint3
     const uint32_t mg = POW2 ? 0u : magic_div(N0);
     const uint32_t sh = POW2 ? (uint32_t)__builtin_ctz(N0) : 0u;
     auto col_of = [&](uint32_t g, uint32_t& e) {
-        const uint32_t hh = POW2 ? g >> sh : __umulhi(g, mg);
-        e = POW2 ? g & (N0 - 1u) : g - hh * N0;
-        return hh;
+        if constexpr (!POW2) return sm_col_magic(g, N0, mg, e);
+        e = g & (N0 - 1u);
+        return g >> sh;
     };
     constexpr uint32_t U = 4;
     const uint32_t total_ev = nh * N0;
     if (((off0 | total_ev) & 1u) == 0u) {         // 16-B aligned start, whole 16-B pairs
         const uint4* blk = reinterpret_cast<const uint4*>(a.events + off0);
         const uint32_t nq = total_ev / 2u;
-        const uint32_t e_lane = POW2 ? (2u * (uint32_t)lane) & (N0 - 1u) : 0u;
-        const uint32_t c_lane = POW2 ? (2u * (uint32_t)lane) >> sh : 0u;
+        // POW2: the lane's pair within a step and its LDS word index, both
+        // a per-lane constant plus a wave-uniform term per load (scatter_map.h)
+        static_assert(U == kScatterLoads, "scatter_map.h: loads per step");
+        const uint32_t lp = sh - 1u;
+        const uint32_t q_lane = POW2 ? sm_lane_pair((uint32_t)lane, lp) : (uint32_t)lane;
+        const uint32_t i_lane = POW2 ? sm_index(q_lane, sh) : 0u;
+        uint32_t* const ev0 = &s_ev[0][0];
         // U x 64 pairs per step: full steps without per-element guards, then the rest
-        auto step = [&](uint32_t k0, auto guard) {
+        auto load = [&](uint32_t k0, uint4 (&x)[U], auto guard) {
             constexpr bool GUARD = decltype(guard)::value;
-            uint4 x[U];
 #pragma unroll
             for (uint32_t u = 0; u < U; ++u) {
-                const uint32_t q = k0 + u * 64u + (uint32_t)lane;
+                const uint32_t q = k0 + (POW2 ? sm_load_pair(u, lp) : u * 64u) + q_lane;
                 // non-temporal: the events are read once per call (they
                 // need not displace the memo tables and saved states in L2;
                 // the driver's command 8.66 vs 8.63e9 over 8 rounds, 200
@@ -350,32 +356,60 @@ __device__ __forceinline__ uint32_t stage_packed_body(const SearchArgs& a, uint3
                     x[u] = make_uint4(0u, 0u, 0u, 0u);
                 }
             }
+        };
+        auto scatter = [&](uint32_t k0, const uint4 (&x)[U], auto guard) {
+            constexpr bool GUARD = decltype(guard)::value;
 #pragma unroll
             for (uint32_t u = 0; u < U; ++u) {
-                const uint32_t q = k0 + u * 64u + (uint32_t)lane;
-                uint32_t e0, e1, c0, c1;
                 if constexpr (POW2) {
                     // an even power-of-two length N0 <= 64: both events of the
-                    // pair in one history (one ds_write2 per pair), the event
-                    // index the lane's own constant (2 (k0 + 64 u) is a multiple
-                    // of N0) and the column a wave-uniform part plus the lane's
-                    e0 = e_lane;
-                    e1 = e_lane + 1u;
-                    c0 = ((2u * (k0 + u * 64u)) >> sh) + c_lane;
-                    c1 = c0;
+                    // pair in one history, rows e and e + 1 of one column (one
+                    // ds_write2 per pair); the word index the lane's constant
+                    // plus a wave-uniform term (2 k0 is a multiple of N0)
+                    const uint32_t q = k0 + sm_load_pair(u, lp) + q_lane;
+                    uint32_t* const w = ev0 + (((2u * k0) >> sh) + sm_index(sm_load_pair(u, lp), sh) + i_lane);
+                    if (!GUARD || q < nq) {
+                        w[0] = word(x[u].x, x[u].y);
+                        w[C_LANES] = word(x[u].z, x[u].w);
+                    }
                 } else {
-                    c0 = col_of(2u * q, e0);
-                    c1 = col_of(2u * q + 1u, e1);
-                }
-                if (!GUARD || q < nq) {
-                    s_ev[e0][c0] = word(x[u].x, x[u].y);
-                    s_ev[e1][c1] = word(x[u].z, x[u].w);
+                    const uint32_t q = k0 + u * 64u + (uint32_t)lane;
+                    uint32_t e0, e1;
+                    const uint32_t c0 = col_of(2u * q, e0);
+                    const uint32_t c1 = col_of(2u * q + 1u, e1);
+                    if (!GUARD || q < nq) {
+                        s_ev[e0][c0] = word(x[u].x, x[u].y);
+                        s_ev[e1][c1] = word(x[u].z, x[u].w);
+                    }
                 }
             }
         };
         uint32_t k0 = 0;
-        for (; k0 + U * 64u <= nq; k0 += U * 64u) step(k0, std::false_type{});
-        if (k0 < nq) step(k0, std::true_type{});
+        // stage 0, a power-of-two block on its first pass (the common packed
+        // batch): two steps' loads in flight together -- a full group of
+        // 32-event histories is two round trips to memory instead of four
+        // (four steps' loads need scratch memory at stage 0's 128 VGPRs, and
+        // in stage 0w they cost an occupancy step)
+        if constexpr (POW2 && DEFER && G::EV == 32) {
+            constexpr uint32_t S = 2;
+            for (; k0 + S * U * 64u <= nq; k0 += S * U * 64u) {
+                uint4 x[S][U];
+#pragma unroll
+                for (uint32_t s = 0; s < S; ++s) load(k0 + s * U * 64u, x[s], std::false_type{});
+#pragma unroll
+                for (uint32_t s = 0; s < S; ++s) scatter(k0 + s * U * 64u, x[s], std::false_type{});
+            }
+        }
+        for (; k0 + U * 64u <= nq; k0 += U * 64u) {
+            uint4 x[U];
+            load(k0, x, std::false_type{});
+            scatter(k0, x, std::false_type{});
+        }
+        if (k0 < nq) {
+            uint4 x[U];
+            load(k0, x, std::true_type{});
+            scatter(k0, x, std::true_type{});
+        }
     } else {
         const uint2* blk = a.events + off0;
         auto step = [&](uint32_t k0, auto guard) {
