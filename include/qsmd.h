@@ -211,6 +211,40 @@ typedef struct qsmd_wtable_model {
     const uint32_t* post_err;  /* same shape, may be NULL (wins over post)     */
 } qsmd_wtable_model;
 
+/* Keyed table model: a map of small states (the shape of the reference's own
+ * Bank model, key -> value) without tabulating the product.  The model is one
+ * *component* table -- a qsmd_table_model within model 3's limits: 256
+ * states, 32 invocation / response symbols -- and n_keys in
+ * 1..QSMD_KTABLE_MAX_KEYS.  The model value is a vector s[0..n_keys) of
+ * component states.  An invocation event carries its component symbol in
+ * `code` and its key in `a`; a response carries its symbol in `code` and its
+ * `a` is ignored; b and val are ignored everywhere.  A step from s with an
+ * invocation (k, i) and a response r is src/Linearisability.hs:63-65 on the
+ * product model:
+ *     postcondition = bit r of post[s[k]][i]
+ *     post_err bit r of [s[k]][i] raises QSMD_STATUS_MODEL_ERROR (wins)
+ *     next state    = s with s[k] := on_resp[on_inv[s[k]][i]][r]
+ * Flat, the same model has n_states^n_keys states (a 4-value register on 8
+ * keys: 65,536 states x 168 invocation symbols, the whole of model 4); keyed,
+ * it is the 4-state table in LDS and 8 bytes of state, searched at model 3's
+ * speed with model 3's search: same verdicts, node counts and witnesses as
+ * the reference on the product model.
+ *
+ * qsmd_check_batch / qsmd_check_batch_device with QSMD_MODEL_KTABLE behave as
+ * documented for QSMD_MODEL_TABLE above, with these differences:
+ *   - model0: NULL = every key at init_state, else a pointer to n_keys
+ *     uint32_t states, each < n_states (QSMD_ERR_ARG otherwise); no keyed
+ *     table set (qsmd_ktable_set): QSMD_ERR_ARG;
+ *   - per history QSMD_STATUS_ENCODE_ERROR also for hdr.model_id != 5 and for
+ *     an invocation whose key (`a`) is >= n_keys;
+ *   - the knob "table_memo" is not served: with it set, a model-5 call runs
+ *     the plain second pass ("table_memo_hits_last" reads 0).  The memo's
+ *     entry holds an 8- or 16-bit state; the keyed state has 64 bits.
+ * "table_budget" and "table_pass2_last" apply unchanged.  A context holds one
+ * narrow, one wide and one keyed table, independently. */
+#define QSMD_MODEL_KTABLE 5u
+#define QSMD_KTABLE_MAX_KEYS 8
+
 /* -------------------------------------------------------------- results */
 
 #define QSMD_STATUS_NONLINEARISABLE 0u  /* linearisable ... == False        */
@@ -280,6 +314,15 @@ int qsmd_table_set(qsmd_ctx* ctx, const qsmd_table_model* model);
  * context keeps its previous wide table.  Waits for the context's last call;
  * the device copy is freed in qsmd_close. */
 int qsmd_wtable_set(qsmd_ctx* ctx, const qsmd_wtable_model* model);
+
+/* Set the context's keyed table model (QSMD_MODEL_KTABLE; one per context,
+ * beside the narrow and the wide one): `component` on n_keys keys.  The rules
+ * of qsmd_table_set for the component (dimensions, every on_inv / on_resp
+ * entry, init_state, the non-NULL tables), and n_keys in
+ * 1..QSMD_KTABLE_MAX_KEYS -- otherwise QSMD_ERR_ARG, and the context keeps
+ * its previous keyed table.  Waits for the context's last call; the device
+ * copy is freed in qsmd_close. */
+int qsmd_ktable_set(qsmd_ctx* ctx, const qsmd_table_model* component, uint32_t n_keys);
 
 /* Threading and streams.  Every entry point of one context serialises on the
  * context's mutex, and the check calls of one context are ordered: a call on

@@ -23,6 +23,7 @@
 #include <vector>
 
 #include "internal.h"
+#include "ktable_host.h"
 #include "qsmd_gen.h"
 #include "tgen.h"
 
@@ -192,6 +193,13 @@ struct qsmd_ctx {
     uint32_t wtab_init = 0;
     bool tm_wide = false;
     uint32_t tm_epoch_w = 0;
+    // QSMD_MODEL_KTABLE (csrc/ktable.hip): the component table set by
+    // qsmd_ktable_set (the narrow format) and its number of keys, beside the
+    // other two.  Its calls use the narrow path's workspace and knobs, and no memo
+    uint32_t* ktab_blob = nullptr;
+    TableDev ktab{};
+    uint32_t ktab_init = 0;
+    uint32_t ktab_keys = 0;
     uint8_t* wf_rank_host = nullptr;   // wellformed: pid rank table (pinned) and its device copy
     char* wf_rank_dev = nullptr;
     size_t wf_rank_bytes = 0;
@@ -402,6 +410,7 @@ void qsmd_close(qsmd_ctx* c) {
     if (c->sx) (void)hipFree(c->sx);
     if (c->tab_blob) (void)hipFree(c->tab_blob);
     if (c->wtab_blob) (void)hipFree(c->wtab_blob);
+    if (c->ktab_blob) (void)hipFree(c->ktab_blob);
     if (c->tws) (void)hipFree(c->tws);
     if (c->tm) (void)hipFree(c->tm);
     if (c->mt) (void)hipFree(c->mt);
@@ -677,6 +686,34 @@ int qsmd_wtable_set(qsmd_ctx* c, const qsmd_wtable_model* m) {
     return QSMD_OK;
 }
 
+int qsmd_ktable_set(qsmd_ctx* c, const qsmd_table_model* m, uint32_t n_keys) {
+    if (!c) return QSMD_ERR_ARG;
+    std::lock_guard<std::mutex> g(c->mu);
+    TableDev t{};
+    std::vector<uint32_t> blob;
+    if (const char* why = ktable_build(m, n_keys, t, blob)) return fail(c, QSMD_ERR_ARG, why);
+    HIP_TRY(c, hipSetDevice(c->device), "hipSetDevice");
+    uint32_t* dev = nullptr;
+    hipError_t e = hipMalloc(reinterpret_cast<void**>(&dev), (size_t)t.blob_words * 4);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(c, QSMD_ERR_NOMEM, "hipMalloc", e);
+    }
+    e = hipMemcpy(dev, blob.data(), (size_t)t.blob_words * 4, hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        (void)hipFree(dev);
+        return fail(c, QSMD_ERR_DEVICE, "H2D table", e);
+    }
+    quiesce(c);                         // the last call may still read the old table
+    if (c->ktab_blob) (void)hipFree(c->ktab_blob);
+    t.blob = dev;
+    c->ktab_blob = dev;
+    c->ktab = t;
+    c->ktab_init = m->init_state;
+    c->ktab_keys = n_keys;
+    return QSMD_OK;
+}
+
 int qsmd_set_time_limit_ms(qsmd_ctx* c, uint64_t ms) {
     if (!c) return QSMD_ERR_ARG;
     c->time_limit_ms = ms;
@@ -800,26 +837,38 @@ enum : uint32_t { kClassesKnown = 8u };
 // One QSMD_MODEL_TABLE call (csrc/table.hip): the binning kernel, per width
 // class pass 1 and (with a budget) pass 2, the totals -- on one stream, no
 // host round trip.  The cascade's workspace and knobs are not touched.
-// WIDE: a QSMD_MODEL_WTABLE call (csrc/wtable.hip), the same launches over
-// the context's wide table.
+// KIND kTabWide: a QSMD_MODEL_WTABLE call (csrc/wtable.hip), the same
+// launches over the context's wide table; kTabKeyed: a QSMD_MODEL_KTABLE call
+// (csrc/ktable.hip) over its keyed table, model0 n_keys states, no memo.
+enum : int { kTabNarrow = 0, kTabWide = 1, kTabKeyed = 2 };
 extern "C++" {
-template <bool WIDE>
+template <int KIND>
 static int check_table_locked(qsmd_ctx* c, const qsmd_hdr* hdr, uint64_t n_hist, const qsmd_event* events,
                               uint64_t n_events, const void* model0, uint32_t flags, uint64_t max_nodes,
                               uint8_t* status, uint64_t* nodes, uint8_t* witness, qsmd_totals* totals,
                               hipStream_t s, uint32_t route) {
+    constexpr bool WIDE = KIND == kTabWide, KEYED = KIND == kTabKeyed;
     if (flags & QSMD_FLAG_EARLY_EXIT_BATCH)
         return fail(c, QSMD_ERR_UNSUPPORTED, "QSMD_FLAG_EARLY_EXIT_BATCH: not for the table models");
     if constexpr (WIDE) {
         if (!c->wtab_blob) return fail(c, QSMD_ERR_ARG, "QSMD_MODEL_WTABLE: no table set (qsmd_wtable_set)");
+    } else if constexpr (KEYED) {
+        if (!c->ktab_blob) return fail(c, QSMD_ERR_ARG, "QSMD_MODEL_KTABLE: no table set (qsmd_ktable_set)");
     } else {
         if (!c->tab_blob) return fail(c, QSMD_ERR_ARG, "QSMD_MODEL_TABLE: no table set (qsmd_table_set)");
     }
     if (n_hist && (!hdr || !status)) return fail(c, QSMD_ERR_ARG, "null hdr/status");
     if (n_hist > 0xFFFFFFFFull) return fail(c, QSMD_ERR_ARG, "n_hist > 2^32-1");
-    const uint32_t state0 = model0 ? *static_cast<const uint32_t*>(model0) : (WIDE ? c->wtab_init : c->tab_init);
-    if (state0 >= (WIDE ? c->wtab.n_states : c->tab.n_states))
-        return fail(c, QSMD_ERR_ARG, "model0: state >= n_states");
+    std::conditional_t<KEYED, uint64_t, uint32_t> state0 = 0;
+    if constexpr (KEYED) {
+        if (!ktable_pack_state(static_cast<const uint32_t*>(model0), c->ktab_init, c->ktab_keys, c->ktab.n_states,
+                               state0))
+            return fail(c, QSMD_ERR_ARG, "model0: state >= n_states");
+    } else {
+        state0 = model0 ? *static_cast<const uint32_t*>(model0) : (WIDE ? c->wtab_init : c->tab_init);
+        if (state0 >= (WIDE ? c->wtab.n_states : c->tab.n_states))
+            return fail(c, QSMD_ERR_ARG, "model0: state >= n_states");
+    }
     HIP_TRY(c, hipSetDevice(c->device), "hipSetDevice");
     HIP_TRY(c, order_after_previous(c, s), "order after the previous call");
 
@@ -828,13 +877,13 @@ static int check_table_locked(qsmd_ctx* c, const qsmd_hdr* hdr, uint64_t n_hist,
     int rc = grow(c, &c->tws, &c->tws_bytes, off_tot + align_up(sizeof(qsmd_totals)));
     if (rc) return rc;
     HIP_TRY(c, hipMemsetAsync(c->tws, 0, kTabHeader, s), "memset header");
-    std::conditional_t<WIDE, WTableArgs, TableArgs> p{};
+    std::conditional_t<WIDE, WTableArgs, std::conditional_t<KEYED, KTableArgs, TableArgs>> p{};
     p.s.hdr = hdr;
     p.s.events = reinterpret_cast<const uint2*>(events);
     p.s.n_hist = n_hist;
     p.s.n_events = n_events;
     p.s.flags = flags;
-    p.s.model_id = WIDE ? QSMD_MODEL_WTABLE : QSMD_MODEL_TABLE;
+    p.s.model_id = WIDE ? QSMD_MODEL_WTABLE : (KEYED ? QSMD_MODEL_KTABLE : QSMD_MODEL_TABLE);
     p.s.max_nodes = max_nodes;
     p.s.time_limit = c->time_limit_ms * 100000ull;   // 100 MHz s_memrealtime
     p.s.status = status;
@@ -843,7 +892,14 @@ static int check_table_locked(qsmd_ctx* c, const qsmd_hdr* hdr, uint64_t n_hist,
     p.s.buckets = reinterpret_cast<unsigned long long*>(c->tws + kTabOffBuckets);
     p.cnt = reinterpret_cast<uint32_t*>(c->tws);
     p.s.timed_out = p.cnt + TC_TIMED;
-    if constexpr (WIDE) p.t = c->wtab; else p.t = c->tab;
+    if constexpr (WIDE) {
+        p.t = c->wtab;
+    } else if constexpr (KEYED) {
+        p.t = c->ktab;
+        p.n_keys = c->ktab_keys;
+    } else {
+        p.t = c->tab;
+    }
     p.state0 = state0;
     for (int k = 0; k < 3; ++k) {
         p.class_list[k] = reinterpret_cast<uint32_t*>(c->tws + kTabHeader + (size_t)k * lst);
@@ -858,7 +914,8 @@ static int check_table_locked(qsmd_ctx* c, const qsmd_hdr* hdr, uint64_t n_hist,
     // CU (the wide tables are not copied: always one per group); pass 2 from
     // the last table call's count.
     const uint64_t groups = std::max<uint64_t>((n_hist + 63) / 64, 1);
-    const uint64_t cap1 = WIDE || (size_t)c->tab.blob_words * 4 <= 4096 ? 65536ull : 8ull * c->n_cu;
+    const size_t lds_blob = WIDE ? 0 : (size_t)(KEYED ? c->ktab : c->tab).blob_words * 4;
+    const uint64_t cap1 = lds_blob <= 4096 ? 65536ull : 8ull * c->n_cu;
     const uint64_t last2 = c->probe_host[kProbeTabPass2];
     // (at least 16 per CU: a workgroup with no group to search returns at
     // once, and the first call has no count -- on 256 workgroups its pass 2
@@ -874,7 +931,9 @@ static int check_table_locked(qsmd_ctx* c, const qsmd_hdr* hdr, uint64_t n_hist,
     // lane slot of pass 2's grid, at most 1 GiB (a smaller grid; one
     // workgroup's tables are always allowed: 2 GiB at 2^20 entries).
     // Entries are tagged by call epoch: cleared when allocated and when the
-    // 24-bit epochs wrap, not per call.
+    // 24-bit epochs wrap, not per call.  (Not for the keyed path: an entry
+    // holds no 64-bit state, so its pass 2 is always the plain one.)
+    if constexpr (!KEYED)
     if (c->table_memo && c->table_budget) {
         const uint64_t per_wg = 64ull * c->table_memo * 32ull;
         uint64_t gm = std::max<uint64_t>((1ull << 30) / per_wg, 1);
@@ -926,12 +985,15 @@ static int check_device_locked(qsmd_ctx* c, uint32_t model_id, const qsmd_hdr* h
                                const qsmd_event* events, uint64_t n_events, const void* model0,
                                uint32_t flags, uint64_t max_nodes, uint8_t* status, uint64_t* nodes,
                                uint8_t* witness, qsmd_totals* totals, hipStream_t s, uint32_t route = 0u) {
+    if (model_id == QSMD_MODEL_KTABLE)
+        return check_table_locked<kTabKeyed>(c, hdr, n_hist, events, n_events, model0, flags, max_nodes, status,
+                                             nodes, witness, totals, s, route);
     if (model_id == QSMD_MODEL_WTABLE)
-        return check_table_locked<true>(c, hdr, n_hist, events, n_events, model0, flags, max_nodes, status, nodes,
-                                        witness, totals, s, route);
+        return check_table_locked<kTabWide>(c, hdr, n_hist, events, n_events, model0, flags, max_nodes, status,
+                                            nodes, witness, totals, s, route);
     if (model_id == QSMD_MODEL_TABLE)
-        return check_table_locked<false>(c, hdr, n_hist, events, n_events, model0, flags, max_nodes, status, nodes,
-                                         witness, totals, s, route);
+        return check_table_locked<kTabNarrow>(c, hdr, n_hist, events, n_events, model0, flags, max_nodes, status,
+                                              nodes, witness, totals, s, route);
     if (model_id != QSMD_MODEL_BANK && model_id != QSMD_MODEL_TICKET)
         return fail(c, QSMD_ERR_ARG, "unknown model_id");
     if (n_hist && (!hdr || !status)) return fail(c, QSMD_ERR_ARG, "null hdr/status");
@@ -1387,7 +1449,7 @@ int qsmd_check_batch(qsmd_ctx* c, uint32_t model_id, const qsmd_hdr* hdr, uint64
     }
     uint32_t route = n_hist == 0 ? 0u : (fits0 ? 0u : kSkip0) | (fits0w || fits0 ? 0u : kSkip0w);
     // the table models: the width classes present (one launch per non-empty class)
-    if (model_id == QSMD_MODEL_TABLE || model_id == QSMD_MODEL_WTABLE) {
+    if (model_id == QSMD_MODEL_TABLE || model_id == QSMD_MODEL_WTABLE || model_id == QSMD_MODEL_KTABLE) {
         route = kClassesKnown;
         for (uint64_t i = 0; i < n_hist && (route & 7u) != 7u; ++i)
             route |= hdr[i].n_ev <= 32u ? 1u : (hdr[i].n_ev <= 64u ? 2u : 4u);
@@ -1682,7 +1744,7 @@ int qsmd_split_frontier(qsmd_ctx* c, uint32_t model_id, const qsmd_hdr* hdr, con
     if (!c) return QSMD_ERR_ARG;
     if (!hdr || !fr || (max_tasks && !tasks_out) || (n_events && !events))
         return fail(c, QSMD_ERR_ARG, "null argument");
-    if (model_id == QSMD_MODEL_TABLE || model_id == QSMD_MODEL_WTABLE)
+    if (model_id == QSMD_MODEL_TABLE || model_id == QSMD_MODEL_WTABLE || model_id == QSMD_MODEL_KTABLE)
         return fail(c, QSMD_ERR_UNSUPPORTED, "split search: not for the table models");
     if (model_id != QSMD_MODEL_BANK && model_id != QSMD_MODEL_TICKET) return fail(c, QSMD_ERR_ARG, "unknown model_id");
     if (max_tasks > (1ull << 24)) return fail(c, QSMD_ERR_ARG, "max_tasks > 2^24");
@@ -1761,7 +1823,7 @@ int qsmd_check_tasks(qsmd_ctx* c, uint32_t model_id, const qsmd_hdr* hdr, const 
     if (!c) return QSMD_ERR_ARG;
     if (!hdr || (n_tasks && (!tasks || !status_out)) || (n_events && !events))
         return fail(c, QSMD_ERR_ARG, "null argument");
-    if (model_id == QSMD_MODEL_TABLE || model_id == QSMD_MODEL_WTABLE)
+    if (model_id == QSMD_MODEL_TABLE || model_id == QSMD_MODEL_WTABLE || model_id == QSMD_MODEL_KTABLE)
         return fail(c, QSMD_ERR_UNSUPPORTED, "split search: not for the table models");
     if (model_id != QSMD_MODEL_BANK && model_id != QSMD_MODEL_TICKET) return fail(c, QSMD_ERR_ARG, "unknown model_id");
     if (n_tasks > (1ull << 24)) return fail(c, QSMD_ERR_ARG, "n_tasks > 2^24");

@@ -467,6 +467,27 @@ struct WTableArgs {
 hipError_t launch_table(const WTableArgs& p, const uint32_t grid1[3], const uint32_t grid2[3], uint32_t classes,
                         hipStream_t s);
 
+// QSMD_MODEL_KTABLE (csrc/ktable.hip): the product of n_keys copies of one
+// narrow component table, searched exactly.  `t` is the component's blob (the
+// narrow format above, copied to LDS by every workgroup); a model value is
+// n_keys component states, key k's in byte k of a 64-bit word.  The
+// workspace, the counters (TCnt) and the probe slots are the narrow path's;
+// there is no state memo (its entry would need the 64-bit state).
+struct KTableArgs {
+    SearchArgs s;
+    TableDev t;                   // the component
+    uint32_t n_keys;              // 1..QSMD_KTABLE_MAX_KEYS
+    uint64_t state0;              // the initial model: key k's state in bits 8k .. 8k + 7
+    uint32_t* cnt;
+    uint32_t* class_list[3];
+    uint32_t* heavy_list[3];
+    uint64_t budget;
+    qsmd_totals* totals;
+    uint32_t* probe_host;
+};
+hipError_t launch_table(const KTableArgs& p, const uint32_t grid1[3], const uint32_t grid2[3], uint32_t classes,
+                        hipStream_t s);
+
 // Early exit: relaxed agent-scope read (a stale value only delays skipping).
 __device__ __forceinline__ bool beyond_first_fail(const SearchArgs& a, uint32_t h) {
     return a.first_fail && h > __hip_atomic_load(a.first_fail, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);

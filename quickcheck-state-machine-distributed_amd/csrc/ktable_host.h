@@ -1,0 +1,59 @@
+// ktable_host.h -- the host half of qsmd_ktable_set (api.hip): everything the
+// keyed kernel will index is checked here, and the component's blob is built
+// in the narrow table's format (internal.h TableDev).  No HIP runtime call,
+// so it is also built and run on its own (tools/ktable_host_check.cpp).
+#pragma once
+
+#include <cstring>
+#include <vector>
+
+#include "internal.h"
+
+namespace qsmd {
+
+// null: `t` (but its device pointer) and `blob` describe the component; else
+// the reason the arguments are refused (nothing is written then).
+inline const char* ktable_build(const qsmd_table_model* m, uint32_t n_keys, TableDev& t,
+                                std::vector<uint32_t>& blob) {
+    if (n_keys == 0 || n_keys > QSMD_KTABLE_MAX_KEYS) return "qsmd_ktable_set: n_keys outside 1..8";
+    if (!m || !m->on_inv || !m->on_resp || !m->post) return "qsmd_ktable_set: null table";
+    if (m->n_states == 0 || m->n_states > QSMD_TABLE_MAX_STATES || m->n_inv == 0 || m->n_inv > QSMD_TABLE_MAX_INV ||
+        m->n_resp == 0 || m->n_resp > QSMD_TABLE_MAX_RESP)
+        return "qsmd_ktable_set: component dimensions outside 1..256 states, 1..32 symbols";
+    if (m->init_state >= m->n_states) return "qsmd_ktable_set: init_state >= n_states";
+    const uint32_t si = m->n_states * m->n_inv, sr = m->n_states * m->n_resp;
+    for (uint32_t k = 0; k < si; ++k)
+        if (m->on_inv[k] >= m->n_states) return "qsmd_ktable_set: on_inv entry >= n_states";
+    for (uint32_t k = 0; k < sr; ++k)
+        if (m->on_resp[k] >= m->n_states) return "qsmd_ktable_set: on_resp entry >= n_states";
+    TableDev d{};
+    d.n_states = m->n_states;
+    d.n_inv = m->n_inv;
+    d.n_resp = m->n_resp;
+    d.has_err = m->post_err ? 1u : 0u;
+    d.blob_words = table_words(d);
+    // (bits at or above n_resp are never read: the kernel checks every code)
+    blob.assign(d.blob_words, 0u);
+    std::memcpy(blob.data(), m->post, (size_t)si * 4);
+    if (m->post_err) std::memcpy(blob.data() + table_off_err(d), m->post_err, (size_t)si * 4);
+    std::memcpy(blob.data() + table_off_inv(d), m->on_inv, si);
+    std::memcpy(blob.data() + table_off_resp(d), m->on_resp, sr);
+    t = d;
+    return nullptr;
+}
+
+// the keyed model value from model0 (n_keys states, null: every key at
+// `init`), key k's state in bits 8k .. 8k + 7; false: a state >= n_states
+inline bool ktable_pack_state(const uint32_t* model0, uint32_t init, uint32_t n_keys, uint32_t n_states,
+                              uint64_t& out) {
+    uint64_t v = 0;
+    for (uint32_t k = 0; k < n_keys; ++k) {
+        const uint32_t s = model0 ? model0[k] : init;
+        if (s >= n_states) return false;
+        v |= (uint64_t)s << (8u * k);
+    }
+    out = v;
+    return true;
+}
+
+}  // namespace qsmd

@@ -7,7 +7,7 @@ HIP kernels (csrc/*.hip, lib/libqsmd.so) behind the C ABI of include/qsmd.h.
 
 from .codec import Left, Right, encode, decode_history, STATUS_NAMES  # noqa: F401
 from .models import (BANK, TICKET, Bank, TicketDispenser, DeviceModel, TableModel, ModelError,  # noqa: F401
-                     EncodeError, WideTableModel)
+                     EncodeError, WideTableModel, KeyedTableModel)
 from .linearisability import (linearisable, linearisable_batch, trace, wellformed,  # noqa: F401
                               replay_witness, CheckResult, NotSequential, BudgetExceeded)
 from . import device, gen  # noqa: F401

@@ -62,6 +62,7 @@ EXPORTS = {
     "qsmd_set_time_limit_ms": (_I, [_P, _U64]),
     "qsmd_table_set": (_I, [_P, _P]),
     "qsmd_wtable_set": (_I, [_P, _P]),
+    "qsmd_ktable_set": (_I, [_P, _P, _U32]),
     "qsmd_set_stage0_grid": (_I, [_P, _U64]),
     "qsmd_set_stage0_budget": (_I, [_P, _U64]),
     "qsmd_probe_read": (_I, [_P, _P]),
@@ -156,6 +157,7 @@ class Context:
         self._check_fn = ctypes.cast(lib.qsmd_check_batch, ctypes.c_void_p).value
         self._table = None              # the models.TableModel this context holds (set_table)
         self._wide_table = None         # the models.WideTableModel it holds (set_wide_table)
+        self._keyed_table = None        # the models.KeyedTableModel it holds (set_keyed_table)
         if time_limit_ms is not None:
             lib.qsmd_set_time_limit_ms(h, int(time_limit_ms))
 
@@ -253,9 +255,22 @@ class Context:
         """The models.WideTableModel set last (None: none)."""
         return self._wide_table
 
+    def set_keyed_table(self, model):
+        """qsmd_ktable_set: make ``model`` (a models.KeyedTableModel) the
+        context's table for QSMD_MODEL_KTABLE calls; a context holds one keyed
+        table, beside the narrow and the wide one."""
+        st = model.component.c_struct()
+        self._check(self._lib.qsmd_ktable_set(self._h, ctypes.byref(st), int(model.n_keys)), "qsmd_ktable_set")
+        self._keyed_table = model
+
+    @property
+    def keyed_table(self):
+        """The models.KeyedTableModel set last (None: none)."""
+        return self._keyed_table
+
     def table_pass2(self):
-        """Histories the second pass took in the most recent QSMD_MODEL_TABLE
-        or QSMD_MODEL_WTABLE call (qsmd_get_param "table_pass2_last")."""
+        """Histories the second pass took in the most recent QSMD_MODEL_TABLE,
+        QSMD_MODEL_WTABLE or QSMD_MODEL_KTABLE call (qsmd_get_param "table_pass2_last")."""
         return self.get_param("table_pass2_last")
 
     def table_memo_hits(self):

@@ -25,7 +25,8 @@ from dataclasses import dataclass, field
 import numpy as np
 
 from . import codec, device
-from .models import BY_ID, BY_NAME, DeviceModel, EncodeError, ModelError, TableModel, WideTableModel
+from .models import (BY_ID, BY_NAME, DeviceModel, EncodeError, KeyedTableModel, ModelError, TableModel,
+                     WideTableModel)
 
 __all__ = ["linearisable", "linearisable_batch", "trace", "wellformed", "replay_witness",
            "CheckResult", "NotSequential", "BudgetExceeded", "wellformed_batch"]
@@ -47,11 +48,15 @@ def _device_model(transition, postcondition) -> DeviceModel:
             and getattr(transition, "__func__", None) is TableModel.transition
             and getattr(postcondition, "__func__", None) is TableModel.postcondition):
         return owner
+    if (isinstance(owner, KeyedTableModel) and getattr(postcondition, "__self__", None) is owner
+            and getattr(transition, "__func__", None) is KeyedTableModel.transition
+            and getattr(postcondition, "__func__", None) is KeyedTableModel.postcondition):
+        return owner
     raise NotImplementedError(
         "no device model for these closures: pass the closures of the reference's Bank "
         "(test/Bank.hs) or TicketDispenser (test/TicketDispenser.hs) models, or tabulate a "
         "finite-state model with qsmd.models.TableModel.from_closures (WideTableModel beyond "
-        "256 states or 32 symbols) and pass its "
+        "256 states or 32 symbols; KeyedTableModel for a map of small states) and pass its "
         ".transition / .postcondition")
 
 
@@ -101,8 +106,11 @@ def linearisable_batch(model, histories, model0=None, *, max_nodes=0, witness=Fa
     if isinstance(m, WideTableModel):
         if ctx.wide_table is not m:
             ctx.set_wide_table(m)
-    elif isinstance(m, TableModel) and ctx.table is not m:
-        ctx.set_table(m)
+    elif isinstance(m, TableModel):
+        if ctx.table is not m:
+            ctx.set_table(m)
+    elif isinstance(m, KeyedTableModel) and ctx.keyed_table is not m:
+        ctx.set_keyed_table(m)
     saved = None
     if table_memo is not None:
         saved = ctx.get_param("table_memo")
@@ -127,7 +135,7 @@ def linearisable(transition, postcondition, model0, history, *, max_nodes=0, ctx
     if st == codec.STATUS_NONLIN:
         return False
     if st == codec.STATUS_MODEL_ERROR:
-        raise ModelError("the postcondition raises" if isinstance(m, TableModel)
+        raise ModelError("the postcondition raises" if isinstance(m, (TableModel, KeyedTableModel))
                          else "Map.!: given key is not an element in the map")
     if st == codec.STATUS_ENCODE_ERROR:
         raise EncodeError(res.batch.encode_errors.get(0, "history cannot be encoded"))
@@ -152,7 +160,7 @@ def trace(transition, model0, history, model: DeviceModel | None = None) -> str:
         for cand in BY_ID.values():
             if transition is cand.transition:
                 m = cand
-        if m is None and isinstance(getattr(transition, "__self__", None), TableModel):
+        if m is None and isinstance(getattr(transition, "__self__", None), (TableModel, KeyedTableModel)):
             m = transition.__self__
         if m is None:
             raise NotImplementedError("trace needs a DeviceModel to show values")

@@ -545,6 +545,118 @@ class WideTableModel(TableModel):
         return (int(entry[r >> 5]) >> (r & 31)) & 1
 
 
+# ---------------------------------------------------------------------------
+# Keyed table models (include/qsmd.h QSMD_MODEL_KTABLE)
+# ---------------------------------------------------------------------------
+
+MODEL_KTABLE = 5
+KTABLE_MAX_KEYS = 8
+
+
+class _Invoked(tuple):
+    """The product state between ``transition m (Left (key, inv))`` and
+    ``transition m' (Right resp)`` (src/Linearisability.hs:64): a response
+    names no key, so the intermediate value remembers the invocation's.  It
+    compares and hashes as the plain tuple."""
+    key = None
+
+
+class KeyedTableModel(DeviceModel):
+    """A map of small states: ``n_keys`` (1..8) independent copies of one
+    ``component`` (a :class:`TableModel`, not a wide one), checked as the
+    product model without tabulating it (``QSMD_MODEL_KTABLE``).
+
+    Model values are tuples of ``n_keys`` component state values, invocation
+    values are ``(key, inv)`` with ``inv`` one of the component's, responses
+    are the component's.  A step from ``s`` with ``(k, i)`` and ``r`` checks
+    the component's postcondition at ``s[k]`` and replaces ``s[k]`` by the
+    component's next state; every other key is unchanged.  ``transition`` and
+    ``postcondition`` are bound methods over those values, so
+    ``linearisable(m.transition, m.postcondition, model0, history)`` finds
+    ``m``."""
+
+    name = "ktable"
+    model_id = MODEL_KTABLE
+
+    def __init__(self, component, n_keys):
+        if not isinstance(component, TableModel) or isinstance(component, WideTableModel):
+            raise EncodeError("the component of a keyed model is a TableModel (256 states, 32 symbols)")
+        if isinstance(n_keys, bool) or not isinstance(n_keys, int) or not 1 <= n_keys <= KTABLE_MAX_KEYS:
+            raise EncodeError(f"n_keys {n_keys!r}: a keyed model has 1..{KTABLE_MAX_KEYS} keys")
+        self.component = component
+        self.n_keys = n_keys
+        self.resps = component.resps
+        self.invs = [(k, i) for k in range(n_keys) for i in component.invs]
+
+    @property
+    def init_model(self):
+        return (self.component.init_model,) * self.n_keys
+
+    def _key(self, k):
+        if isinstance(k, bool) or not isinstance(k, int) or not 0 <= k < self.n_keys:
+            raise EncodeError(f"key {k!r}: this keyed model has keys 0..{self.n_keys - 1}")
+        return k
+
+    def _split(self, inv):
+        try:
+            k, i = inv
+        except (TypeError, ValueError):
+            raise EncodeError(f"not a (key, inv) invocation: {inv!r}") from None
+        return self._key(k), i
+
+    def _model(self, m):
+        if not isinstance(m, tuple) or len(m) != self.n_keys:
+            raise EncodeError(f"not a state of this keyed model ({self.n_keys} component states): {m!r}")
+        return m
+
+    # bound methods: linearisable() finds the model through their __self__
+    def transition(self, m, ev):
+        kind, x = ev
+        m = self._model(m)
+        if kind == "L":
+            k, i = self._split(x)
+            out = _Invoked(m[:k] + (self.component.transition(m[k], ("L", i)),) + m[k + 1:])
+            out.key = k
+            return out
+        k = getattr(m, "key", None)
+        if k is None:       # (no invocation before it: nothing to apply the response to)
+            return tuple(m)
+        return m[:k] + (self.component.transition(m[k], ("R", x)),) + m[k + 1:]
+
+    def postcondition(self, m, inv, resp):
+        k, i = self._split(inv)
+        return self.component.postcondition(self._model(m)[k], i, resp)
+
+    def encode_inv(self, inv, accounts):
+        k, i = self._split(inv)
+        return self.component.encode_inv(i, None)[0], k, 0, 0
+
+    def encode_resp(self, resp):
+        return self.component.encode_resp(resp)
+
+    def decode_inv(self, code, a, b, val, accounts):
+        return (a, self.component.invs[code])
+
+    def decode_resp(self, code, val):
+        return self.component.resps[code]
+
+    def pack_model0(self, model0, accounts):
+        """``n_keys`` uint32 component states (a ctypes array), None for init_model."""
+        if model0 is None:
+            return None
+        return (ctypes.c_uint32 * self.n_keys)(*[self.component._state(s) for s in self._model(model0)])
+
+    def show_model(self, model):
+        return "{" + ", ".join(f"{k}: {self.component.show_model(s)}" for k, s in enumerate(model)) + "}"
+
+    def show_inv(self, inv):
+        k, i = self._split(inv)
+        return f"[{k}] {self.component.show_inv(i)}"
+
+    def show_resp(self, resp):
+        return self.component.show_resp(resp)
+
+
 TICKET = TicketDispenser()
 BANK = Bank()
 

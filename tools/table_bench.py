@@ -26,8 +26,16 @@ explicit --distinct D the first D generated histories are tiled to --n on the
 device instead, which isolates what tiling does to the measurement.  Without
 the flag the tool does exactly what it did before it had one.
 
+--keyed K: the keyed path (csrc/ktable.hip, QSMD_MODEL_KTABLE).  K = 1 runs
+the register batch above as QSMD_MODEL_TABLE and as KeyedTableModel(register,
+1), the same histories, interleaved: what the keyed step costs.  K > 1 runs
+4x16 histories of the register on K keys (tests/ktablegen.py's product
+generator) as QSMD_MODEL_KTABLE and, re-encoded, as QSMD_MODEL_WTABLE on the
+flat product (4^K states, 21 K invocations; K <= 4 tabulates in seconds),
+interleaved: what factoring buys.  Not with --generated, --wide or --model kv.
+
     python tools/table_bench.py [--budgets default,0] [--memo 0,64,256,1024,4096] [--distinct 65536] [--n 1048576]
-                                [--wide 0|1|both] [--model register|kv] [--generated] [--seed S]
+                                [--wide 0|1|both] [--model register|kv] [--generated] [--seed S] [--keyed K]
 """
 
 import argparse
@@ -45,7 +53,7 @@ for p in ("quickcheck-state-machine-distributed_amd", "oracle", "tests"):
 
 import tablegen as tg  # noqa: E402
 from qsmd import codec, device, gen  # noqa: E402
-from qsmd.models import TableModel, WideTableModel  # noqa: E402
+from qsmd.models import KeyedTableModel, TableModel, WideTableModel  # noqa: E402
 
 
 def main():
@@ -62,7 +70,10 @@ def main():
     ap.add_argument("--model", default="register", choices=["register", "kv"])
     ap.add_argument("--generated", action="store_true")
     ap.add_argument("--seed", type=int, default=0x7AB1E)
+    ap.add_argument("--keyed", type=int, default=0)
     args = ap.parse_args()
+    if args.keyed and (args.generated or args.wide != "0" or args.model != "register"):
+        ap.error("--keyed runs the register model alone, from host-generated histories")
     tiled = args.distinct is not None or not args.generated
     if args.distinct is None:
         args.distinct = 65536 if tiled else args.n
@@ -83,9 +94,22 @@ def main():
         ctx.set_table(m)
     if 4 in ids:
         ctx.set_wide_table(m if isinstance(m, WideTableModel) else WideTableModel.from_closures(*closures))
+    encoders = {mid: m for mid in ids}      # model id -> the model that encodes the batch for it
+    if args.keyed:
+        import ktablegen as kg
+        km = KeyedTableModel(m, args.keyed)
+        ctx.set_keyed_table(km)
+        if args.keyed == 1:
+            ids, encoders = [3, 5], {3: m, 5: km}
+        else:
+            model = kg.product(model, args.keyed)
+            flat = WideTableModel.from_closures(model["transition"], model["postcondition"], model["init"],
+                                                model["invs"], model["resps"])
+            ctx.set_wide_table(flat)
+            ids, encoders = [5, 4], {5: km, 4: flat}
     reps = (args.n + args.distinct - 1) // args.distinct
     n = reps * args.distinct
-    d_hdrs = {}
+    d_hdrs, d_evs = {}, {}
     if args.generated:
         per = 32
         gp = gen.table_params(n_clients=4, n_ops=16, prefix_ops=0, lin_policy=gen.LIN_AT_INVOKE,
@@ -105,24 +129,29 @@ def main():
             d_hdrs[mid] = h
         if reps > 1:
             d_ev = d_ev[:args.distinct * per * 8].repeat(reps)
+        d_evs[ids[0]] = d_ev
         n_events = n * per
         what = (f"{args.model} 4x16 generated on the device (seed {args.seed:#x}, p_bug 0.39), " +
                 (f"{args.distinct} distinct tiled to {n}" if reps > 1 else f"{n} distinct"))
     else:
         rng = random.Random("table_bench")
         hists = [tg.gen_history(model, rng, 4, 16, 0.03) for _ in range(args.distinct)]
-        batch = codec.encode(m, hists)
-        per = len(batch.events)
-        hdr = np.tile(batch.hdr, reps)
-        hdr["ev_off"] = (hdr["ev_off"].astype(np.int64) + np.repeat(np.arange(reps, dtype=np.int64) * per,
-                                                                     args.distinct)).astype(np.uint32)
-        ev = np.tile(batch.events, reps)
-        for mid in ids:                     # the same batch, only hdr.model_id changed
+        for mid in ids:                     # the same histories, in each model's encoding
+            hs = hists
+            if args.keyed == 1 and mid == 5:        # the one key
+                hs = [[(p, (k, (0, x) if k == "L" else x)) for p, (k, x) in h] for h in hists]
+            batch = codec.encode(encoders[mid], hs)
+            assert not batch.encode_errors
+            per = len(batch.events)
+            hdr = np.tile(batch.hdr, reps)
+            hdr["ev_off"] = (hdr["ev_off"].astype(np.int64) + np.repeat(np.arange(reps, dtype=np.int64) * per,
+                                                                         args.distinct)).astype(np.uint32)
             hdr["model_id"] = mid
             d_hdrs[mid] = torch.from_numpy(hdr.view(np.uint8).copy()).to(dev)
-        d_ev = torch.from_numpy(ev.view(np.uint8)).to(dev)
-        n_events = len(ev)
-        what = f"{args.model} 4x16 p_bug 0.03, {args.distinct} distinct tiled to {n}, device-resident"
+            if args.keyed or not d_evs:     # (without --keyed the events are the same for every id: one copy)
+                d_evs[mid] = torch.from_numpy(np.tile(batch.events, reps).view(np.uint8)).to(dev)
+        n_events = per * reps
+        what = f"{model['name']} 4x16 p_bug 0.03, {args.distinct} distinct tiled to {n}, device-resident"
     d_st = torch.empty(n, dtype=torch.uint8, device=dev)
     d_nd = torch.empty(n, dtype=torch.int64, device=dev)
     d_tot = torch.zeros(8, dtype=torch.int64, device=dev)
@@ -130,7 +159,7 @@ def main():
     cross = [(b, int(e), mid) for _ in range(args.rounds) for b in args.budgets.split(",")
              for e in args.memo.split(",") for mid in ids]
     for b, entries, mid in cross:
-        d_hdr = d_hdrs[mid]
+        d_hdr, d_ev = d_hdrs[mid], d_evs.get(mid, next(iter(d_evs.values())))
         budget = default if b == "default" else int(b)
         ctx.set_param("table_budget", budget)
         ctx.set_param("table_memo", entries)
