@@ -237,9 +237,18 @@ typedef struct qsmd_wtable_model {
  *     table set (qsmd_ktable_set): QSMD_ERR_ARG;
  *   - per history QSMD_STATUS_ENCODE_ERROR also for hdr.model_id != 5 and for
  *     an invocation whose key (`a`) is >= n_keys;
- *   - the knob "table_memo" is not served: with it set, a model-5 call runs
- *     the plain second pass ("table_memo_hits_last" reads 0).  The memo's
- *     entry holds an 8- or 16-bit state; the keyed state has 64 bits.
+ *   - the second pass's exact-count state memo has its own knob here,
+ *     "ktable_memo" (default 0 = off: the plain second pass; else a power of
+ *     two in 2..2^20 entries per lane slot, anything else QSMD_ERR_ARG and
+ *     the old value stays).  The rule is "table_memo"'s on (remaining events,
+ *     the full 64-bit state): status, node count and witness are unchanged,
+ *     a max_nodes inside a folded subtree gives BUDGET with nodes ==
+ *     max_nodes.  An entry is 48 bytes; the tables share "table_memo"'s
+ *     allocation (first use, QSMD_ERR_NOMEM, the 1 GiB cap -- one workgroup's
+ *     tables always allowed, 3 GiB at 2^20 entries -- and "table_memo_grid").
+ *     "table_memo_hits_last" reads its hits after a model-5 call.
+ *     "table_memo" has no effect on model 5, "ktable_memo" none on models 3
+ *     and 4.
  * "table_budget" and "table_pass2_last" apply unchanged.  A context holds one
  * narrow, one wide and one keyed table, independently. */
 #define QSMD_MODEL_KTABLE 5u

@@ -185,21 +185,26 @@ struct qsmd_ctx {
     uint32_t tm_epoch = 0;
     // QSMD_MODEL_WTABLE (csrc/wtable.hip): the wide table set by
     // qsmd_wtable_set, beside the narrow one.  Its calls use the narrow
-    // path's workspace, knobs and memo tables; the two paths tag a memo entry
-    // differently (epoch 24 | state 8 against 16 | 16), so the tables are
-    // cleared when the path that wrote them last is not the one about to run
+    // path's workspace, knobs and memo tables; the paths lay a memo entry out
+    // differently (narrow: epoch 24 | state 8, wide: 16 | 16, keyed: 48-byte
+    // entries), so the tables are cleared when the path that wrote them last
+    // (tm_wide: kTabNarrow / kTabWide / kTabKeyed) is not the one about to run
     uint32_t* wtab_blob = nullptr;
     WTableDev wtab{};
     uint32_t wtab_init = 0;
-    bool tm_wide = false;
+    int tm_wide = 0;
     uint32_t tm_epoch_w = 0;
     // QSMD_MODEL_KTABLE (csrc/ktable.hip): the component table set by
     // qsmd_ktable_set (the narrow format) and its number of keys, beside the
-    // other two.  Its calls use the narrow path's workspace and knobs, and no memo
+    // other two.  Its calls use the narrow path's workspace, budget and memo
+    // allocation; its memo has its own knob ("ktable_memo", entries per lane
+    // slot; 0 = off) and its own epochs (a full word)
     uint32_t* ktab_blob = nullptr;
     TableDev ktab{};
     uint32_t ktab_init = 0;
     uint32_t ktab_keys = 0;
+    uint64_t ktable_memo = 0;
+    uint32_t tm_epoch_k = 0;
     uint8_t* wf_rank_host = nullptr;   // wellformed: pid rank table (pinned) and its device copy
     char* wf_rank_dev = nullptr;
     size_t wf_rank_bytes = 0;
@@ -533,6 +538,10 @@ int qsmd_set_param(qsmd_ctx* c, const char* name, uint64_t value) {
         if (value && (value < 2 || value > (1ull << 20) || (value & (value - 1))))
             return fail(c, QSMD_ERR_ARG, "table_memo: 0 (off) or a power of two in 2..2^20");
         c->table_memo = value;
+    } else if (n == "ktable_memo") {        // the keyed path's own: QSMD_MODEL_KTABLE calls only
+        if (!ktable_memo_ok(value))
+            return fail(c, QSMD_ERR_ARG, "ktable_memo: 0 (off) or a power of two in 2..2^20");
+        c->ktable_memo = value;
     } else if (n == "table_memo_grid") {    // diagnostic: pass 2's workgroups at most with the memo (0 = automatic)
         if (value > 65536) return fail(c, QSMD_ERR_ARG, "table_memo_grid in 0..65536");
         c->table_memo_grid = value;
@@ -839,7 +848,7 @@ enum : uint32_t { kClassesKnown = 8u };
 // host round trip.  The cascade's workspace and knobs are not touched.
 // KIND kTabWide: a QSMD_MODEL_WTABLE call (csrc/wtable.hip), the same
 // launches over the context's wide table; kTabKeyed: a QSMD_MODEL_KTABLE call
-// (csrc/ktable.hip) over its keyed table, model0 n_keys states, no memo.
+// (csrc/ktable.hip) over its keyed table, model0 n_keys states, the memo under its own knob.
 enum : int { kTabNarrow = 0, kTabWide = 1, kTabKeyed = 2 };
 extern "C++" {
 template <int KIND>
@@ -931,15 +940,25 @@ static int check_table_locked(qsmd_ctx* c, const qsmd_hdr* hdr, uint64_t n_hist,
     // lane slot of pass 2's grid, at most 1 GiB (a smaller grid; one
     // workgroup's tables are always allowed: 2 GiB at 2^20 entries).
     // Entries are tagged by call epoch: cleared when allocated and when the
-    // 24-bit epochs wrap, not per call.  (Not for the keyed path: an entry
-    // holds no 64-bit state, so its pass 2 is always the plain one.)
-    if constexpr (!KEYED)
-    if (c->table_memo && c->table_budget) {
-        const uint64_t per_wg = 64ull * c->table_memo * 32ull;
-        uint64_t gm = std::max<uint64_t>((1ull << 30) / per_wg, 1);
-        if (c->table_memo_grid) gm = std::min<uint64_t>(gm, c->table_memo_grid);
-        gm = std::min<uint64_t>(gm, g2);
-        const size_t need = (size_t)(gm * per_wg);
+    // 24-bit epochs wrap, not per call.  The keyed path has its own knob
+    // ("ktable_memo"; "table_memo" does not reach it, nor "ktable_memo" the
+    // other two), 48-byte entries and full-word epochs; its sizing is
+    // ktable_memo_plan (ktable_host.h).
+    const uint64_t memo_entries = KEYED ? c->ktable_memo : c->table_memo;
+    if (memo_entries && c->table_budget) {
+        uint64_t gm;
+        size_t need;
+        if constexpr (KEYED) {
+            const KMemoPlan plan = ktable_memo_plan(memo_entries, g2, c->table_memo_grid);
+            gm = plan.grid;
+            need = (size_t)plan.bytes;
+        } else {
+            const uint64_t per_wg = 64ull * memo_entries * 32ull;
+            gm = std::max<uint64_t>((1ull << 30) / per_wg, 1);
+            if (c->table_memo_grid) gm = std::min<uint64_t>(gm, c->table_memo_grid);
+            gm = std::min<uint64_t>(gm, g2);
+            need = (size_t)(gm * per_wg);
+        }
         if (c->tm_bytes < need) {
             if (c->tm) {
                 quiesce(c);
@@ -955,19 +974,20 @@ static int check_table_locked(qsmd_ctx* c, const qsmd_hdr* hdr, uint64_t n_hist,
             }
             c->tm_bytes = need;
             HIP_TRY(c, hipMemsetAsync(c->tm, 0, c->tm_bytes, s), "memset table memo");
-        } else if (c->tm_wide != WIDE) {    // the other path's entries: their tag word reads differently
+        } else if (c->tm_wide != KIND) {    // another path's entries: their words read differently
             HIP_TRY(c, hipMemsetAsync(c->tm, 0, c->tm_bytes, s), "memset table memo");
         }
-        c->tm_wide = WIDE;
-        // (narrow: 24-bit epochs beside an 8-bit state; wide: 16 beside 16)
-        uint32_t& epoch = WIDE ? c->tm_epoch_w : c->tm_epoch;
-        constexpr uint32_t kEpochMask = WIDE ? 0xFFFFu : 0xFFFFFFu;
+        c->tm_wide = KIND;
+        // (narrow: 24-bit epochs beside an 8-bit state; wide: 16 beside 16;
+        // keyed: a word of its own)
+        uint32_t& epoch = WIDE ? c->tm_epoch_w : (KEYED ? c->tm_epoch_k : c->tm_epoch);
+        constexpr uint32_t kEpochMask = WIDE ? 0xFFFFu : (KEYED ? 0xFFFFFFFFu : 0xFFFFFFu);
         if (((++epoch) & kEpochMask) == 0u) {        // the tags wrapped: clear
             HIP_TRY(c, hipMemsetAsync(c->tm, 0, c->tm_bytes, s), "memset table memo");
             ++epoch;
         }
         p.memo = reinterpret_cast<uint4*>(c->tm);
-        p.memo_entries = (uint32_t)c->table_memo;
+        p.memo_entries = (uint32_t)memo_entries;
         p.memo_epoch = epoch & kEpochMask;
         for (int k = 0; k < 3; ++k) grid2[k] = (uint32_t)gm;
     }
@@ -1702,6 +1722,8 @@ int qsmd_get_param(qsmd_ctx* c, const char* name, uint64_t* out) {
         *out = c->probe_host[kProbeTabPass2];
     } else if (n == "table_memo") {
         *out = c->table_memo;
+    } else if (n == "ktable_memo") {
+        *out = c->ktable_memo;
     } else if (n == "table_memo_grid") {
         *out = c->table_memo_grid;
     } else if (n == "table_memo_hits_last") {   // memo hits of the most recent QSMD_MODEL_TABLE call

@@ -471,8 +471,9 @@ hipError_t launch_table(const WTableArgs& p, const uint32_t grid1[3], const uint
 // narrow component table, searched exactly.  `t` is the component's blob (the
 // narrow format above, copied to LDS by every workgroup); a model value is
 // n_keys component states, key k's in byte k of a 64-bit word.  The
-// workspace, the counters (TCnt) and the probe slots are the narrow path's;
-// there is no state memo (its entry would need the 64-bit state).
+// workspace, the counters (TCnt) and the probe slots are the narrow path's.
+// Pass 2's state memo is its own (knob "ktable_memo"): an entry holds the
+// 64-bit state, 3 x uint4 (ktable_host.h, ktable.hip KTableMemo).
 struct KTableArgs {
     SearchArgs s;
     TableDev t;                   // the component
@@ -484,6 +485,10 @@ struct KTableArgs {
     uint64_t budget;
     qsmd_totals* totals;
     uint32_t* probe_host;
+    uint4* memo;                  // pass 2's state memo ("ktable_memo"): grid2 x 64 tables of memo_entries
+                                  // entries of 3 x uint4, or null (off: the plain pass 2)
+    uint32_t memo_entries;        // a power of two
+    uint32_t memo_epoch;          // this call's tag: a full word, never 0
 };
 hipError_t launch_table(const KTableArgs& p, const uint32_t grid1[3], const uint32_t grid2[3], uint32_t classes,
                         hipStream_t s);

@@ -24,7 +24,27 @@
 //     component has at most 32 symbols; a response's key bits are 0), in
 //     col16's paired words, so the per-lane indexed reads of a divergent
 //     wavefront stay conflict-free and the LDS bytes are model 3's.
-// There is no state memo: with "table_memo" set pass 2 is the plain one.
+//
+// Pass 2's exact-count state memo (knob "ktable_memo") is
+// table.hip's rule (TableDFS::step<MEMO>) on S = (rem, the full 64-bit
+// state): the backtrack branch records (S of the node being left, the nodes
+// counted since its entry) before rem and state are restored; after a
+// descent S of the child is probed, and a hit counts the recorded nodes and
+// backtracks at once (or ends as BUDGET when the limit falls inside them).  A
+// raising step, a time-limit stop and a budget stop record nothing.  One
+// direct-mapped table of "ktable_memo" entries per lane slot of pass 2's
+// grid, in HBM.  One entry size for every width class, 48 B = 3 x uint4:
+//     [0]  count lo | count hi | epoch (the call's, a full word) | history index
+//     [1]  state lo | state hi | rem word 0 | rem word 1
+//     [2]  rem word 2 | rem word 3 | 0 | 0        (128-event class only)
+// The 32- and 64-event classes read and write [0] and [1] only (their rem
+// word 1 / words 2-3 do not exist).  The epoch and the history index stand in
+// the same place for every class, so an entry left by another class or
+// another call never matches: a hit compares epoch, history, both state
+// words and every rem word, never the hash alone.  The slot is a
+// multiplicative hash of the rem words and both state words; table.hip's
+// 64-bit map of written slots (mod 64) gates the HBM probe.  "table_memo"
+// has no effect here: with "ktable_memo" 0 pass 2 is the plain one.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -50,6 +70,65 @@ struct KTabLds {
 // the staged event: its symbol, its key (invocations)
 __device__ __forceinline__ uint32_t kev_code(uint32_t e) { return (e >> 8) & 31u; }
 __device__ __forceinline__ uint32_t kev_key(uint32_t e) { return e >> 13; }
+
+// One lane's view of pass 2's state memo (the header comment): its table in
+// HBM, its LDS column of node counts at entry per level, the map of written
+// slots.  tlane::TableMemo with the 64-bit state and the 3 x uint4 entry.
+template <class M>
+struct KTableMemo {
+    static constexpr int NW = TW<M>::NW;
+    uint4* tab;             // the lane's table
+    uint64_t* entry;        // LDS: [level][lane], this lane's column
+    uint32_t mask;          // entries - 1
+    uint32_t epoch;         // the call's tag (never 0: cleared tables match nothing)
+    uint32_t h;
+    uint32_t hits;
+    uint64_t wr;
+    bool skip;              // the node being left was a hit: recorded already
+
+    __device__ __forceinline__ uint32_t slot_of(const uint32_t* w, uint64_t state) const {
+        constexpr uint32_t K[4] = {0x9E3779B1u, 0x85EBCA77u, 0xC2B2AE3Du, 0x27D4EB2Fu};
+        uint32_t x = (uint32_t)state * 0x165667B1u ^ (uint32_t)(state >> 32) * 0xD6E8FEB9u;
+#pragma unroll
+        for (int k = 0; k < NW; ++k) x ^= w[k] * K[k];
+        x ^= x >> 16;
+        x *= 0x85EBCA6Bu;
+        x ^= x >> 13;
+        return x & mask;
+    }
+    __device__ __forceinline__ void begin(uint32_t hist) {
+        h = hist;
+        wr = 0ull;
+        skip = false;
+    }
+    __device__ __forceinline__ void record(const M& rem, uint64_t state, uint64_t count) {
+        uint32_t w[4] = {0u, 0u, 0u, 0u};
+        to_words(rem, w);
+        const uint32_t slot = slot_of(w, state);
+        uint4* e = tab + 3u * slot;
+        e[0] = make_uint4((uint32_t)count, (uint32_t)(count >> 32), epoch, h);
+        e[1] = make_uint4((uint32_t)state, (uint32_t)(state >> 32), w[0], w[1]);
+        if constexpr (NW > 2) e[2] = make_uint4(w[2], w[3], 0u, 0u);
+        wr |= 1ull << (slot & 63u);
+    }
+    // the whole key is compared: epoch, history, both state words, every rem word
+    __device__ __forceinline__ bool probe(const M& rem, uint64_t state, uint64_t& count) const {
+        uint32_t w[4] = {0u, 0u, 0u, 0u};
+        to_words(rem, w);
+        const uint32_t slot = slot_of(w, state);
+        if (!((wr >> (slot & 63u)) & 1ull)) return false;
+        const uint4* e = tab + 3u * slot;
+        const uint4 a = e[0], b = e[1];
+        count = a.x | ((uint64_t)a.y << 32);
+        bool same = a.z == epoch && a.w == h && b.x == (uint32_t)state && b.y == (uint32_t)(state >> 32) &&
+                    b.z == w[0] && b.w == w[1];
+        if constexpr (NW > 2) {
+            const uint4 c = e[2];
+            same = same && c.x == w[2] && c.y == w[3];
+        }
+        return same;
+    }
+};
 
 // One lane's search state (registers) over its LDS columns: table.hip's
 // TableDFS with the keyed step.
@@ -93,14 +172,23 @@ struct KTableDFS {
     // candidate.  -1 = go on, kTerm = the search ended (finish()), or
     // QSMD_STATUS_BUDGET (limit nodes counted; nothing moved) /
     // QSMD_STATUS_MODEL_ERROR.
+    // MEMO (pass 2 with "ktable_memo"): a subtree left by a backtrack is
+    // recorded with the nodes it counted, a descent into a recorded (rem,
+    // state) counts them and backtracks at once.
+    template <bool MEMO>
     __device__ __forceinline__ int step(const TableDev& t, const KTabLds& L, const uint16_t* ev, uint16_t* stk,
-                                        int lane, uint64_t limit) {
+                                        int lane, uint64_t limit, KTableMemo<M>& mm) {
         const bool empty = !MO::any(cand);
         if (empty && (found == 0u || depth == 0u)) return kTerm;
         if (empty) {
             // backtrack: the parent's remaining set by Lemma L1, the one
             // component the step changed from the stack
             --depth;
+            if constexpr (MEMO) {
+                // (rem, state) are still the node's being left
+                if (!mm.skip) mm.record(rem, state, nodes - mm.entry[depth * C_LANES]);
+                mm.skip = false;
+            }
             const uint32_t st = stk[col16(depth, lane)];
             const uint32_t j = st & 0xFFu;
             const uint32_t shift = kev_key(ev[col16(j, lane)]) * 8u;
@@ -136,6 +224,22 @@ struct KTableDFS {
             rem = rem & ~(MO::lowest(rem & pmj & INV) | MO::bit((int)r));
             cand = t_cands(rem, INV, RESP);
             found = 0u;
+            if constexpr (MEMO) {
+                mm.entry[(depth - 1u) * C_LANES] = nodes;
+                uint64_t c;
+                if (mm.probe(rem, state, c)) {
+                    ++mm.hits;
+                    uint64_t sum;
+                    if (__builtin_add_overflow(nodes, c, &sum) || sum > limit) {   // the budget falls inside that subtree
+                        nodes = limit;
+                        return QSMD_STATUS_BUDGET;
+                    }
+                    nodes = sum;                 // the subtree's nodes, counted; it failed
+                    cand = t_zero<M>();
+                    found = 1u;
+                    mm.skip = true;
+                }
+            }
         }
         return -1;
     }
@@ -219,7 +323,9 @@ __global__ __launch_bounds__(C_LANES) void ktable_bin(KTableArgs a) {
 
 // PASS2 false: the class list with the pass-1 budget; true: the class's
 // heavy list, every search to its end.
-template <class M>
+// MEMO: pass 2 with the state memo (a.memo: one table of a.memo_entries
+// entries per lane slot of the grid).
+template <class M, bool MEMO>
 __global__ __launch_bounds__(C_LANES) void ktable_search(KTableArgs a, uint32_t pass2) {
     constexpr int EV = TW<M>::EV, K = TW<M>::CLASS;
     extern __shared__ uint32_t lds[];
@@ -228,10 +334,19 @@ __global__ __launch_bounds__(C_LANES) void ktable_search(KTableArgs a, uint32_t 
     const uint32_t total = a.cnt[(pass2 ? TC_HEAVY : TC_CLASS) + K];
     if ((uint64_t)blockIdx.x * C_LANES >= total) return;
 
-    // LDS: events [EV / 2][64] words, stack [EV / 4][64] words, the component's tables
+    // LDS: events [EV / 2][64] words, stack [EV / 4][64] words, (MEMO: the
+    // node counts at entry, [EV / 2][64] u64,) the component's tables
     uint16_t* ev = reinterpret_cast<uint16_t*>(lds);
     uint16_t* stk = reinterpret_cast<uint16_t*>(lds + (EV / 2) * C_LANES);
-    uint32_t* tab = lds + (EV / 2 + EV / 4) * C_LANES;
+    uint32_t* tab = lds + (EV / 2 + EV / 4 + (MEMO ? EV : 0)) * C_LANES;
+    KTableMemo<M> mm;
+    if constexpr (MEMO) {
+        mm.entry = reinterpret_cast<uint64_t*>(lds + (EV / 2 + EV / 4) * C_LANES) + lane;
+        mm.tab = a.memo + ((uint64_t)blockIdx.x * C_LANES + (uint64_t)lane) * (uint64_t)a.memo_entries * 3ull;
+        mm.mask = a.memo_entries - 1u;
+        mm.epoch = a.memo_epoch;
+        mm.hits = 0u;
+    }
     {
         const uint4* src = reinterpret_cast<const uint4*>(a.t.blob);
         uint4* dst = reinterpret_cast<uint4*>(tab);
@@ -266,11 +381,12 @@ __global__ __launch_bounds__(C_LANES) void ktable_search(KTableArgs a, uint32_t 
             status = stage_ktable<M>(a, H, ev, lane, dfs) ? -1 : QSMD_STATUS_ENCODE_ERROR;
             if (status == -1) dfs.init(a.state0);
         }
+        if constexpr (MEMO) mm.begin(h);
         // the search, the time limit checked every 1024 iterations (a
         // wavefront-uniform counter: the loop runs while any lane searches)
         while (__ballot(status == -1) != 0ull) {
             for (uint32_t k = 0; k < 1024u; ++k) {
-                if (status == -1) status = dfs.step(a.t, L, ev, stk, lane, limit);
+                if (status == -1) status = dfs.template step<MEMO>(a.t, L, ev, stk, lane, limit, mm);
                 if (__ballot(status == -1) == 0ull) break;
             }
             if (status == -1 && a.s.time_limit && __builtin_amdgcn_s_memrealtime() - t0 > a.s.time_limit) {
@@ -293,6 +409,14 @@ __global__ __launch_bounds__(C_LANES) void ktable_search(KTableArgs a, uint32_t 
             }
         }
         cnt.add(out, status, dfs.nodes);
+        if constexpr (MEMO) {
+            // the group's hits: one atomic per wavefront
+            const uint64_t hits = wave_sum64(mm.hits);
+            mm.hits = 0u;
+            if (lane == 0 && hits)
+                __hip_atomic_fetch_add(reinterpret_cast<unsigned long long*>(a.cnt + TC_HITS), (unsigned long long)hits,
+                                       __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
     }
     cnt.flush(a.s.buckets, lane);
 }
@@ -309,21 +433,21 @@ __global__ __launch_bounds__(C_LANES) void ktable_finish(KTableArgs a) {
         a.probe_host[C_TIMED] = a.cnt[TC_TIMED];
         a.probe_host[kProbeTabPass2] = a.cnt[TC_HEAVY] + a.cnt[TC_HEAVY + 1] + a.cnt[TC_HEAVY + 2];
         for (int c = 0; c < 3; ++c) a.probe_host[kProbeTabClass + c] = a.cnt[TC_CLASS + c];
-        a.probe_host[kProbeTabHits] = 0u;       // no memo
-        a.probe_host[kProbeTabHits + 1] = 0u;
+        a.probe_host[kProbeTabHits] = a.cnt[TC_HITS];
+        a.probe_host[kProbeTabHits + 1] = a.cnt[TC_HITS + 1];
         __threadfence_system();
     }
 }
 
-template <class M>
+template <class M, bool MEMO>
 hipError_t launch_class(const KTableArgs& p, uint32_t grid, uint32_t pass2, hipStream_t s) {
-    const size_t lds = table_lds_bytes(p.t, TW<M>::CLASS);
+    const size_t lds = table_lds_bytes(p.t, TW<M>::CLASS, MEMO);
     if (lds > 64u * 1024u) {
         static std::atomic<int> set[kAttrDevices];
-        const hipError_t e = ensure_dyn_lds(reinterpret_cast<const void*>(&ktable_search<M>), set, lds);
+        const hipError_t e = ensure_dyn_lds(reinterpret_cast<const void*>(&ktable_search<M, MEMO>), set, lds);
         if (e != hipSuccess) return e;
     }
-    hipLaunchKernelGGL((ktable_search<M>), dim3(grid), dim3(C_LANES), lds, s, p, pass2);
+    hipLaunchKernelGGL((ktable_search<M, MEMO>), dim3(grid), dim3(C_LANES), lds, s, p, pass2);
     return hipGetLastError();
 }
 
@@ -336,9 +460,15 @@ hipError_t launch_table(const KTableArgs& p, const uint32_t grid1[3], const uint
     hipError_t e = hipGetLastError();
     for (uint32_t pass2 = 0; pass2 < (p.budget ? 2u : 1u) && e == hipSuccess; ++pass2) {
         const uint32_t* g = pass2 ? grid2 : grid1;
-        if (e == hipSuccess && (classes & 1u)) e = launch_class<uint32_t>(p, g[0], pass2, s);
-        if (e == hipSuccess && (classes & 2u)) e = launch_class<uint64_t>(p, g[1], pass2, s);
-        if (e == hipSuccess && (classes & 4u)) e = launch_class<M128>(p, g[2], pass2, s);
+        if (pass2 && p.memo) {
+            if (e == hipSuccess && (classes & 1u)) e = launch_class<uint32_t, true>(p, g[0], pass2, s);
+            if (e == hipSuccess && (classes & 2u)) e = launch_class<uint64_t, true>(p, g[1], pass2, s);
+            if (e == hipSuccess && (classes & 4u)) e = launch_class<M128, true>(p, g[2], pass2, s);
+            continue;
+        }
+        if (e == hipSuccess && (classes & 1u)) e = launch_class<uint32_t, false>(p, g[0], pass2, s);
+        if (e == hipSuccess && (classes & 2u)) e = launch_class<uint64_t, false>(p, g[1], pass2, s);
+        if (e == hipSuccess && (classes & 4u)) e = launch_class<M128, false>(p, g[2], pass2, s);
     }
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(ktable_finish, dim3(1), dim3(C_LANES), 0, s, p);

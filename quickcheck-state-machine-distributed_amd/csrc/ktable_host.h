@@ -1,7 +1,9 @@
 // ktable_host.h -- the host half of qsmd_ktable_set (api.hip): everything the
 // keyed kernel will index is checked here, and the component's blob is built
-// in the narrow table's format (internal.h TableDev).  No HIP runtime call,
-// so it is also built and run on its own (tools/ktable_host_check.cpp).
+// in the narrow table's format (internal.h TableDev); and the sizing of the
+// keyed path's state memo ("ktable_memo").  No HIP runtime call, so it is
+// also built and run on its own (tools/ktable_host_check.cpp,
+// tools/ktable_memo_host_check.cpp).
 #pragma once
 
 #include <cstring>
@@ -54,6 +56,41 @@ inline bool ktable_pack_state(const uint32_t* model0, uint32_t init, uint32_t n_
     }
     out = v;
     return true;
+}
+
+// Pass 2's state memo on the keyed path (knob "ktable_memo", ktable.hip
+// KTableMemo): one direct-mapped table of `entries` entries per lane slot of
+// pass 2's grid.  One entry size for every width class: 3 x uint4 (count 64 |
+// epoch 32 | history 32, state 64 | rem words 0-1, rem words 2-3 | zero); the
+// 32- and 64-event classes never touch the third.
+constexpr uint32_t kKMemoEntryBytes = 48;
+constexpr uint64_t kKMemoCapBytes = 1ull << 30;
+constexpr uint64_t kKMemoMaxEntries = 1ull << 20;
+
+// the knob's values: 0 (off) or a power of two in 2..2^20
+inline bool ktable_memo_ok(uint64_t v) { return v == 0 || (v >= 2 && v <= kKMemoMaxEntries && (v & (v - 1)) == 0); }
+
+struct KMemoPlan {
+    uint32_t entry_bytes;
+    uint64_t per_wg;              // bytes of one workgroup's 64 tables
+    uint32_t grid;                // pass 2's workgroups with the memo
+    uint64_t bytes;               // grid * per_wg: the allocation
+};
+// entries: an accepted non-zero knob value; grid2 >= 1: pass 2's grid without
+// the memo; grid_cap: "table_memo_grid" (0 = none).  The tables are held to
+// 1 GiB by a smaller grid, but one workgroup's are always allowed (3 GiB at
+// 2^20 entries).  64 * 2^20 * 48 * 65536 < 2^64: no overflow.
+inline KMemoPlan ktable_memo_plan(uint64_t entries, uint64_t grid2, uint64_t grid_cap) {
+    KMemoPlan p{};
+    p.entry_bytes = kKMemoEntryBytes;
+    p.per_wg = 64ull * entries * kKMemoEntryBytes;
+    uint64_t g = kKMemoCapBytes / p.per_wg;
+    if (g < 1) g = 1;
+    if (grid_cap && g > grid_cap) g = grid_cap;
+    if (g > grid2) g = grid2;
+    p.grid = (uint32_t)g;
+    p.bytes = g * p.per_wg;
+    return p;
 }
 
 }  // namespace qsmd

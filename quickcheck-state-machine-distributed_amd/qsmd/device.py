@@ -274,8 +274,9 @@ class Context:
         return self.get_param("table_pass2_last")
 
     def table_memo_hits(self):
-        """Hits of the second pass's state memo (knob "table_memo") in the
-        most recent QSMD_MODEL_TABLE call (qsmd_get_param
+        """Hits of the second pass's state memo (knob "table_memo"; for a
+        QSMD_MODEL_KTABLE call "ktable_memo") in the most recent table call
+        (qsmd_get_param
         "table_memo_hits_last")."""
         return self.get_param("table_memo_hits_last")
 

@@ -97,7 +97,9 @@ def linearisable_batch(model, histories, model0=None, *, max_nodes=0, witness=Fa
                        flags=device.QSMD_FLAG_EXHAUSTIVE, ctx=None, table_memo=None) -> CheckResult:
     """Check many histories in one device call.  ``table_memo`` (table models:
     entries per lane slot of the second pass's state memo, 0 = off) sets the
-    context's "table_memo" knob for this call and restores it afterwards."""
+    context's "table_memo" knob for this call and restores it afterwards;
+    with a :class:`KeyedTableModel` the knob is the keyed path's own,
+    "ktable_memo"."""
     m = _as_model(model)
     batch = codec.encode(m, histories, model0)
     accounts0 = m.new_account_map(model0)
@@ -112,15 +114,16 @@ def linearisable_batch(model, histories, model0=None, *, max_nodes=0, witness=Fa
     elif isinstance(m, KeyedTableModel) and ctx.keyed_table is not m:
         ctx.set_keyed_table(m)
     saved = None
+    knob = "ktable_memo" if isinstance(m, KeyedTableModel) else "table_memo"
     if table_memo is not None:
-        saved = ctx.get_param("table_memo")
-        ctx.set_param("table_memo", table_memo)
+        saved = ctx.get_param(knob)
+        ctx.set_param(knob, table_memo)
     try:
         status, nodes, wit, totals = ctx.check_arrays(m.model_id, batch.hdr, batch.events, packed,
                                                       flags, max_nodes, witness)
     finally:
         if saved is not None:
-            ctx.set_param("table_memo", saved)
+            ctx.set_param(knob, saved)
     return CheckResult(batch, status, nodes, wit, totals)
 
 

@@ -33,6 +33,8 @@ the register batch above as QSMD_MODEL_TABLE and as KeyedTableModel(register,
 generator) as QSMD_MODEL_KTABLE and, re-encoded, as QSMD_MODEL_WTABLE on the
 flat product (4^K states, 21 K invocations; K <= 4 tabulates in seconds),
 interleaved: what factoring buys.  Not with --generated, --wide or --model kv.
+--memo sizes the keyed path's memo through its own knob ("ktable_memo") on
+the model-5 lines and "table_memo" on the others; every line carries the hits.
 
     python tools/table_bench.py [--budgets default,0] [--memo 0,64,256,1024,4096] [--distinct 65536] [--n 1048576]
                                 [--wide 0|1|both] [--model register|kv] [--generated] [--seed S] [--keyed K]
@@ -162,7 +164,9 @@ def main():
         d_hdr, d_ev = d_hdrs[mid], d_evs.get(mid, next(iter(d_evs.values())))
         budget = default if b == "default" else int(b)
         ctx.set_param("table_budget", budget)
-        ctx.set_param("table_memo", entries)
+        # (the keyed path's memo has its own knob; each knob is set for its own path alone)
+        ctx.set_param("table_memo", 0 if mid == 5 else entries)
+        ctx.set_param("ktable_memo", entries if mid == 5 else 0)
         ms = []
         for k in range(args.warmup + args.calls):
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -179,7 +183,7 @@ def main():
             "model_id": mid,
             "workload": what,
             "table_budget": budget, "is_default": budget == default, "table_memo": entries,
-            "table_memo_hits": ctx.table_memo_hits(), "calls": args.calls,
+            "memo_knob": "ktable_memo" if mid == 5 else "table_memo", "table_memo_hits": ctx.table_memo_hits(), "calls": args.calls,
             "ms_per_call_median": round(med, 4), "ms_min": round(min(ms), 4), "ms_max": round(max(ms), 4),
             "histories_per_s": round(n / med * 1e3), "nodes_per_s": round(int(tot[7]) / med * 1e3),
             "nodes_per_call": int(tot[7]), "pass2_histories": ctx.table_pass2(),
