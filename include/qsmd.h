@@ -456,9 +456,14 @@ int qsmd_set_stage0_budget(qsmd_ctx* ctx, uint64_t nodes);
  *   "timing_events"     1: record the per-call timing events (qsmd_timing_read,
  *                       qsmd_last_kernel_ms); 0 (default until
  *                       qsmd_timing_reset): none
- *   "giant_grid"        giant stage workgroups (0 = 2 per CU, or 64 when the
- *                       last finished call had no giant history and lane
- *                       mode's fold does not apply)
+ *   "giant_grid"        giant stage workgroups (0 = automatic: 1 when the last
+ *                       finished call had no giant, deferred nothing and had
+ *                       no wide history and this is no early-exit call -- a
+ *                       call that has giants after all runs them on that
+ *                       grid, once; 2 per CU before any call has finished,
+ *                       after a call with giants and on lane mode's folded
+ *                       route; an early-exit call without them: one per
+ *                       fixup chunk, 8 to 2 per CU; else 64)
  *   "wave_stats_ptr", "memo_stats_ptr", "memo_stats_groups"  diagnostics:
  *                       device buffers: wave mode 16 x u64 (DFS iterations
  *                       max / sum, s_memtime cycles max / sum, nodes sum per
@@ -473,8 +478,9 @@ int qsmd_set_stage0_budget(qsmd_ctx* ctx, uint64_t nodes);
 int qsmd_set_param(qsmd_ctx* ctx, const char* name, uint64_t value);
 
 /* Read a knob ("table_budget", "stage0_budget": 0 while automatic, "stage0w_budget_auto", "fold",
- * "heavy_mode", "memo_after", "resume_cap", "tail_cap", "tail_min", "heavy_buckets") or
- * "stage0_budget_last": the stage-0 budget the most recent
+ * "heavy_mode", "memo_after", "resume_cap", "tail_cap", "tail_min", "heavy_buckets", "giant_grid"),
+ * "giant_grid_last": the giant stage's workgroups in the most recent Bank /
+ * Ticket check call, or "stage0_budget_last": the stage-0 budget the most recent
  * finished check call ran with (the automatic one included; waits for the
  * context's last call). */
 int qsmd_get_param(qsmd_ctx* ctx, const char* name, uint64_t* out);

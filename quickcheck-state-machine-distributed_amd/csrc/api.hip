@@ -104,7 +104,8 @@ struct qsmd_ctx {
     unsigned long long* memo_stats = nullptr;   // diagnostic (memo_stats_ptr): 16 x u64 per heavy-stage group
     uint64_t memo_stats_groups = 0;             // (memo_stats_groups)
     uint32_t memo_lds = 1;                      // heavy-stage memo tables in LDS: 0 never, 1 short lists, 2 always
-    uint64_t giant_grid = 0;           // giant stage workgroups (0 = 2 per CU)
+    uint64_t giant_grid = 0;           // giant stage workgroups (0 = by the last call's probe, below)
+    uint64_t giant_grid_last = 0;      // ... of the most recent Bank / Ticket call
     uint64_t giant_stall_us = 0;       // diagnostic: the giant stage's first frontier chunk starts this late
     unsigned long long* s0_stamps = nullptr;    // diagnostic (stage0_stamps_ptr): 8 x u64 per stage-0 workgroup
     // heavy stage: one wavefront per history (wave_search, csrc/wave.hip)
@@ -213,6 +214,7 @@ struct qsmd_ctx {
 namespace {
 
 constexpr uint32_t kStage0wGrid = 1024;
+constexpr uint64_t kGiantIdleGrid = 1;   // giant stage workgroups of a call expected to hold no giant
 constexpr size_t kZeroCopyBytes = 64 * 1024;   // host calls this small run on a mapped host buffer
 constexpr uint64_t kTimingSlots = 1024;
 constexpr uint64_t kSlotEvents = 5;      // stage 0 start / end, call end, heavy start / end
@@ -1350,12 +1352,24 @@ static int check_device_locked(qsmd_ctx* c, uint32_t model_id, const qsmd_hdr* h
         // early exit without them: one workgroup per fixup chunk, at least 8
         // and at most 2 per CU -- every workgroup of the launch takes the
         // fixup's queue and exit atomics, 2 per CU made a 4096-history call's
-        // giant stage ~65 us)
+        // giant stage ~65 us).
+        // Nothing expected -- the last finished call had no giant, deferred
+        // nothing and had no wide history, and this is no early-exit call:
+        // kGiantIdleGrid workgroups, on the folded route too.  Each workgroup
+        // of the launch needs 64.5 KB of LDS and 256 registers of one SIMD
+        // only to return, on CUs the calls in flight keep full of stage-0
+        // groups (profiles/inflight_tail/).  The stage takes its work from
+        // queues and "last workgroup out" counts gridDim.x, so a call that
+        // has giants after all runs them on this grid, once: its probe puts
+        // the next call back on 2 per CU.
+        const bool idle = c->probe_valid && !early && hint[3] == 0u && hint[0] == 0u && hint[kProbeWide] == 0u;
         const uint64_t gg = c->giant_grid ? c->giant_grid
+                          : idle ? kGiantIdleGrid
                           : (hint[3] || (fold && !early) ? 2ull * c->n_cu
                                      : (early ? std::min<uint64_t>(2ull * c->n_cu,
                                                                    std::max<uint64_t>(8, (n_hist + kFixupChunk - 1) / kFixupChunk))
                                               : 64ull));
+        c->giant_grid_last = gg;
         if (sync_stages()) p.debug = giant_debug_buffer(c, gg);
         HIP_TRY(c, launch_giants(p, (uint32_t)gg, s), "giant launch");
         if (sync_stages()) giant_heartbeat(c, s, gg);
@@ -1705,6 +1719,10 @@ int qsmd_get_param(qsmd_ctx* c, const char* name, uint64_t* out) {
         *out = c->resume_cap;
     } else if (n == "fold") {
         *out = c->fold;
+    } else if (n == "giant_grid") {
+        *out = c->giant_grid;
+    } else if (n == "giant_grid_last") {     // giant stage workgroups of the most recent check call
+        *out = c->giant_grid_last;
     } else if (n == "heavy_mode") {
         *out = c->heavy_mode;
     } else if (n == "memo_after") {
