@@ -186,6 +186,92 @@ int qsmd_gen_table_batch_device(qsmd_ctx* ctx, const qsmd_gen_table_params* p,
                                 qsmd_event* events_dev, uint8_t* bug_dev,
                                 void* stream);
 
+/* ---------------------------------------------- keyed-table-model generator
+ *
+ * The same generator for QSMD_MODEL_KTABLE (include/qsmd.h): n_keys copies of
+ * one narrow component table.  The stream is the table-model stream above on
+ * the PRODUCT model, kept factored; the host function (csrc/gen/ktgen.cpp),
+ * the device kernel (csrc/ktgen.hip) and the tests' restatement
+ * (tests/ktablegen_ref.py) emit identical bytes from this definition.
+ *
+ * Unchanged from the table-model generator: the RNG with next(), below(n)
+ * and unit(); the schedule, steps 1-4 (the prefix, the S client draws, the
+ * ticks, the bug step with n_resp the component's); execute's "stuck" flag;
+ * the header fields and ev_base; the flag byte.  What differs:
+ *
+ *   State.  s[0 .. n_keys) are component state indices, every key starting
+ *     at the component's init_state.
+ *   Invocation symbol.  A pair (k, i): key k < n_keys, i one of the
+ *     component's n_inv invocation symbols.
+ *   acc(s, (k, i)) = the component's acc(s[k], i) (post & ~post_err, bits at
+ *     or above n_resp cleared).
+ *   weight(k, i) = key_weight[k] * inv_weight[i], the product formed in 64
+ *     bits; a NULL array counts as all 1.
+ *   request(s), ONE draw over the pairs in ascending (k, i), key-major (k
+ *     outer, i inner): a pair is enabled when weight(k, i) > 0 and
+ *     acc(s, (k, i)) != 0.  W = the sum of the enabled weights; if W == 0,
+ *     every pair with weight(k, i) > 0 is enabled instead and W is their sum.
+ *     w = below(W); the invocation is the first pair, in that order, whose
+ *     running sum of enabled weights exceeds w.
+ *   execute(s, (k, i)), one draw, as for the component at s[k]: A =
+ *     acc(s[k], i).  If A != 0, r is the below(popcount(A))-th set bit of A;
+ *     otherwise r = below(n_resp) and the flag byte gets bit 1.  Then
+ *     s[k] = on_resp[on_inv[s[k]][i]][r]; no other key changes.
+ *   Events.  An invocation event is {kp = pid, code = i, a = k, b = 0, val =
+ *     0}; a response event {kp = 0x80 | pid, code = r, 0, 0, 0}.
+ *     hdr.model_id = QSMD_MODEL_KTABLE (5).
+ *
+ * So the keyed stream equals the QSMD_MODEL_WTABLE stream on the flat product
+ * with invocation symbol k * n_inv + i and weight key_weight[k] *
+ * inv_weight[i], code c re-encoded as (a = c / n_inv, code = c % n_inv).
+ *
+ * Promise.  As above, on the product: with QSMD_GEN_PID_PER_CLIENT a history
+ * whose flag byte is 0 is linearisable from the initial vector (every key at
+ * init_state), its execute points being a witness.  The same caveats hold:
+ * for a component with post_err and QSMD_GEN_LIN_IN_WINDOW the reference's
+ * search, and so the checker, may still report MODEL_ERROR for such a
+ * history (it raises on a branch it tries before the witness; with
+ * QSMD_GEN_LIN_AT_INVOKE it cannot); and with QSMD_GEN_PID_SHARED there is NO
+ * promise, since the checker pairs an invocation with the first remaining
+ * response of its pid (Q1), which may be another client's. */
+typedef struct qsmd_gen_ktable_params {
+    uint32_t n_keys;       /* 1..QSMD_KTABLE_MAX_KEYS                             */
+    uint32_t n_clients;    /* C, 1..32                                            */
+    uint32_t n_ops;        /* K, 1..64                                            */
+    uint32_t prefix_ops;   /* sequential prefix, clamped to K                     */
+    uint32_t lin_policy;   /* QSMD_GEN_LIN_*                                       */
+    uint32_t pid_mode;     /* QSMD_GEN_PID_*                                       */
+    uint32_t overlap;      /* max operations outstanding at once (0 = C)          */
+    double   p_bug;        /* probability of one injected response bug, in [0, 1] */
+    uint64_t seed;
+    const uint32_t* inv_weight;  /* n_inv weights (host pointer); NULL = all 1    */
+    const uint32_t* key_weight;  /* n_keys weights (host pointer); NULL = all 1   */
+} qsmd_gen_ktable_params;
+
+/* Generate histories [first, first + n_hist) of the keyed stream from
+ * `component` (host pointers) on p->n_keys keys.  events holds n_hist * 2 *
+ * n_ops entries.  QSMD_ERR_ARG, with no output written: everything
+ * qsmd_ktable_set rejects in the component or in n_keys, C outside 1..32, K
+ * outside 1..64, lin_policy or pid_mode above 1, p_bug NaN or outside [0, 1],
+ * weights whose pairwise products are all zero or sum past 2^32 - 1,
+ * ev_base + n_hist * 2 * K past 2^32 - 1. */
+int qsmd_gen_ktable_batch(const qsmd_gen_ktable_params* p, const qsmd_table_model* component,
+                          uint64_t first, uint64_t n_hist, uint32_t ev_base,
+                          qsmd_hdr* hdr, qsmd_event* events, uint8_t* bug_out,
+                          int n_threads);
+
+/* On-device generation (libqsmd.so, csrc/ktgen.hip) of the same stream,
+ * byte-identical, from the keyed table the context holds (qsmd_ktable_set;
+ * none set, or p->n_keys different from the context's: QSMD_ERR_ARG).
+ * Buffers and stream as for qsmd_gen_batch_device; the weights are host
+ * pointers, read before the call returns.  The call is one of the context's
+ * ordered calls: it waits for the previous one, and a later qsmd_ktable_set
+ * waits for it before it frees the component. */
+int qsmd_gen_ktable_batch_device(qsmd_ctx* ctx, const qsmd_gen_ktable_params* p,
+                                 uint64_t first, uint64_t n_hist, uint32_t ev_base,
+                                 qsmd_hdr* hdr_dev, qsmd_event* events_dev,
+                                 uint8_t* bug_dev, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -25,6 +25,7 @@
 #include "internal.h"
 #include "ktable_host.h"
 #include "qsmd_gen.h"
+#include "ktgen.h"
 #include "tgen.h"
 
 #include "qsmd.h"
@@ -1612,6 +1613,78 @@ int qsmd_gen_table_batch_device(qsmd_ctx* c, const qsmd_gen_table_params* p, uin
     if (!s) return fail(c, QSMD_ERR_DEVICE, "hipStreamCreate");
     HIP_TRY(c, order_after_previous(c, s), "order after the previous call");
     HIP_TRY(c, launch_tgen(a, (uint32_t)c->n_cu, s), "table gen launch");
+    const bool own = s == c->stream;
+    if (!own) HIP_TRY(c, hipEventRecord(c->done_ev, s), "hipEventRecord");
+    c->done_last = !own;
+    c->last_stream = s;
+    c->in_flight = true;
+    return QSMD_OK;
+}
+
+// The keyed table models' generator (csrc/ktgen.hip).  One of the context's
+// ordered calls: it reads the context's keyed component, which
+// qsmd_ktable_set frees once the last call is done.
+int qsmd_gen_ktable_batch_device(qsmd_ctx* c, const qsmd_gen_ktable_params* p, uint64_t first, uint64_t n_hist,
+                                 uint32_t ev_base, qsmd_hdr* hdr_dev, qsmd_event* events_dev, uint8_t* bug_dev,
+                                 void* stream) {
+    if (!c) return QSMD_ERR_ARG;
+    std::lock_guard<std::mutex> g(c->mu);
+    // the parameter checks of qsmd_gen_ktable_batch (csrc/gen/ktgen.cpp)
+    if (!p || (n_hist && (!hdr_dev || !events_dev))) return fail(c, QSMD_ERR_ARG, "null params/buffers");
+    if (!c->ktab_blob) return fail(c, QSMD_ERR_ARG, "no keyed table set (qsmd_ktable_set)");
+    if (p->n_keys != c->ktab_keys) return fail(c, QSMD_ERR_ARG, "n_keys differs from the context's keyed table");
+    if (p->n_clients < 1 || p->n_clients > 32) return fail(c, QSMD_ERR_ARG, "n_clients outside 1..32");
+    if (p->n_ops < 1 || 2 * p->n_ops > QSMD_MAX_EVENTS) return fail(c, QSMD_ERR_ARG, "n_ops outside 1..64");
+    if (p->lin_policy > 1 || p->pid_mode > 1) return fail(c, QSMD_ERR_ARG, "lin_policy / pid_mode");
+    if (!(p->p_bug >= 0.0 && p->p_bug <= 1.0)) return fail(c, QSMD_ERR_ARG, "p_bug outside [0, 1]");
+    if ((uint64_t)ev_base + n_hist * 2ull * p->n_ops > 0xFFFFFFFFull || n_hist > 0xFFFFFFFFull)
+        return fail(c, QSMD_ERR_ARG, "ev_off beyond u32");
+    KTGenArgs a{};
+    uint64_t w_all = 0;       // at most 256 products, each held to 2^32 - 1
+    a.w_unit = 1u;
+    for (uint32_t i = 0; i < c->ktab.n_inv; ++i) {
+        const uint32_t w = a.inv_weight[i] = p->inv_weight ? p->inv_weight[i] : 1u;
+        if (w > 1u) a.w_unit = 0u;
+        if (w) a.w_mask |= 1u << i;
+    }
+    for (uint32_t k = 0; k < p->n_keys; ++k) {
+        const uint32_t kw = a.key_weight[k] = p->key_weight ? p->key_weight[k] : 1u;
+        if (kw > 1u) a.w_unit = 0u;
+        if (kw) a.k_mask |= 1u << k;
+        for (uint32_t i = 0; i < c->ktab.n_inv; ++i) {
+            const uint64_t w = (uint64_t)kw * a.inv_weight[i];
+            if (w > 0xFFFFFFFFull) return fail(c, QSMD_ERR_ARG, "key_weight * inv_weight past 2^32 - 1");
+            w_all += w;
+        }
+    }
+    if (w_all == 0 || w_all > 0xFFFFFFFFull)
+        return fail(c, QSMD_ERR_ARG, "weights: every product zero or a sum past 2^32 - 1");
+    if (n_hist == 0) return QSMD_OK;
+    a.t = c->ktab;
+    a.state0 = c->ktab_init;
+    a.n_keys = p->n_keys;
+    a.n_clients = p->n_clients;
+    a.n_ops = p->n_ops;
+    a.prefix = std::min(p->prefix_ops, p->n_ops);
+    a.in_window = p->lin_policy == QSMD_GEN_LIN_IN_WINDOW;
+    a.shared = p->pid_mode == QSMD_GEN_PID_SHARED;
+    a.overlap = p->overlap ? p->overlap : p->n_clients;
+    a.w_all = (uint32_t)w_all;
+    // (the integer form of unit() < p_bug: qsmd_gen_table_batch_device)
+    a.bug_draw = p->p_bug > 0.0;
+    a.bug_below = (uint64_t)std::ceil(std::ldexp(p->p_bug, 53));
+    a.seed = p->seed;
+    a.first = first;
+    a.n_hist = n_hist;
+    a.ev_base = ev_base;
+    a.hdr = hdr_dev;
+    a.events = events_dev;
+    a.bug = bug_dev;
+    HIP_TRY(c, hipSetDevice(c->device), "hipSetDevice");
+    hipStream_t s = stream ? static_cast<hipStream_t>(stream) : ctx_stream(c);
+    if (!s) return fail(c, QSMD_ERR_DEVICE, "hipStreamCreate");
+    HIP_TRY(c, order_after_previous(c, s), "order after the previous call");
+    HIP_TRY(c, launch_ktgen(a, (uint32_t)c->n_cu, s), "keyed table gen launch");
     const bool own = s == c->stream;
     if (!own) HIP_TRY(c, hipEventRecord(c->done_ev, s), "hipEventRecord");
     c->done_last = !own;

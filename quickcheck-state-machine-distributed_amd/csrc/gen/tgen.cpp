@@ -7,37 +7,11 @@
 // at its linearisation point.  The header's comment is the definition; this
 // file follows it line by line (the device kernel, csrc/tgen.hip, keeps the
 // same stream in registers and LDS).
-#include "qsmd_gen.h"
-
-#include <algorithm>
-#include <cstring>
-#include <thread>
-#include <vector>
+#include "tgen_stream.h"
 
 namespace {
 
-struct Rng {  // xoshiro256** seeded by splitmix64 (gen.cpp's)
-    uint64_t s[4];
-    static uint64_t splitmix(uint64_t& x) {
-        uint64_t z = (x += 0x9E3779B97F4A7C15ull);
-        z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-        z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-        return z ^ (z >> 31);
-    }
-    Rng(uint64_t seed, uint64_t index) {
-        uint64_t x = seed ^ (index * 0xD1B54A32D192ED03ull);
-        for (auto& v : s) v = splitmix(x);
-    }
-    static uint64_t rotl(uint64_t x, int k) { return (x << k) | (x >> (64 - k)); }
-    uint64_t next() {
-        const uint64_t r = rotl(s[1] * 5, 7) * 9, t = s[1] << 17;
-        s[2] ^= s[0]; s[3] ^= s[1]; s[1] ^= s[2]; s[0] ^= s[3];
-        s[2] ^= t; s[3] = rotl(s[3], 45);
-        return r;
-    }
-    uint32_t below(uint32_t n) { return n ? (uint32_t)((next() >> 32) * n >> 32) : 0; }
-    double unit() { return (next() >> 11) * (1.0 / 9007199254740992.0); }
-};
+using qsmd_tgen::Rng;
 
 // Either table behind one face: acc(s, i) as post_words words.
 struct Model {
@@ -73,10 +47,15 @@ struct Model {
 };
 
 struct Gen {
-    const qsmd_gen_table_params& p;
+    using State = uint32_t;
+    using Sym = uint32_t;
     const Model& m;
     const uint32_t* weight;        // n_inv entries
     uint32_t w_all;                // the sum of all weights
+
+    State init() const { return m.init_state; }
+    uint32_t n_resp() const { return m.n_resp; }
+    qsmd_event inv_event(uint8_t kp, Sym i) const { return qsmd_event{kp, (uint8_t)i, 0, 0, 0}; }
 
     uint32_t request(Rng& r, uint32_t s) const {
         uint32_t a[QSMD_WTABLE_MAX_RESP / 32];
@@ -118,80 +97,6 @@ struct Gen {
         s = m.resp_to(m.inv_to(s, i), resp);
         return resp;
     }
-
-    void one(uint64_t index, qsmd_event* ev, uint8_t* flag_out) const {
-        Rng r(p.seed, index);
-        const uint32_t C = p.n_clients, K = p.n_ops;
-        const uint32_t P = std::min(p.prefix_ops, K), S = K - P;
-        const uint32_t overlap = p.overlap ? p.overlap : C;
-        const bool shared = p.pid_mode == QSMD_GEN_PID_SHARED;
-        uint32_t s = m.init_state;
-        uint8_t flags = 0;
-        uint32_t ne = 0;
-        auto emit = [&](uint32_t c, bool resp, uint32_t code) {
-            ev[ne++] = qsmd_event{(uint8_t)((resp ? QSMD_EV_RESP : 0u) | (shared ? 0u : c)), (uint8_t)code, 0, 0, 0};
-        };
-
-        for (uint32_t k = 0; k < P; ++k) {
-            const uint32_t c = r.below(C);
-            const uint32_t i = request(r, s);
-            const uint32_t x = execute(r, s, i, flags);
-            emit(c, false, i);
-            emit(c, true, x);
-        }
-
-        uint32_t queued[32] = {}, inv[32] = {}, resp[32] = {};
-        uint8_t st[32] = {};                      // 0 idle, 1 invoked, 2 executed
-        for (uint32_t k = 0; k < S; ++k) queued[r.below(C)]++;
-        uint32_t outstanding = 0, done = 0;
-        uint32_t act[32];
-        while (done < S) {
-            uint32_t n_act = 0;
-            for (uint32_t c = 0; c < C; ++c)
-                if (st[c] ? true : (queued[c] && outstanding < overlap)) act[n_act++] = c;
-            const uint32_t c = act[r.below(n_act)];
-            if (st[c] == 0) {
-                inv[c] = request(r, s);
-                emit(c, false, inv[c]);
-                queued[c]--;
-                outstanding++;
-                if (p.lin_policy == QSMD_GEN_LIN_AT_INVOKE) {
-                    resp[c] = execute(r, s, inv[c], flags);
-                    st[c] = 2;
-                } else {
-                    st[c] = 1;
-                }
-            } else if (st[c] == 1) {
-                resp[c] = execute(r, s, inv[c], flags);
-                st[c] = 2;
-            } else {
-                emit(c, true, resp[c]);
-                st[c] = 0;
-                outstanding--;
-                done++;
-            }
-        }
-
-        if (p.p_bug > 0 && r.unit() < p.p_bug && S >= 1) {
-            uint32_t at[64], n = 0;               // the suffix responses' positions
-            for (uint32_t e = 2 * P; e < ne; ++e)
-                if (ev[e].kp & QSMD_EV_RESP) at[n++] = e;
-            const bool two = m.n_resp >= 2;
-            const uint32_t coin = two && S >= 2 ? r.below(2) : 0u;
-            if (two && (S < 2 || coin == 0)) {
-                const uint32_t e = at[r.below(S)];
-                ev[e].code = (uint8_t)((ev[e].code + 1u + r.below(m.n_resp - 1)) % m.n_resp);
-                flags |= 1u;
-            } else if (S >= 2) {
-                const uint32_t k1 = r.below(S);
-                uint32_t k2 = r.below(S);
-                if (k2 == k1) k2 = (k1 + 1) % S;
-                std::swap(ev[at[k1]].code, ev[at[k2]].code);
-                flags |= 1u;
-            }
-        }
-        if (flag_out) *flag_out = flags;
-    }
 };
 
 template <class T, class S>
@@ -231,39 +136,16 @@ extern "C" int qsmd_gen_table_batch(const qsmd_gen_table_params* p, const void* 
     } else {
         return QSMD_ERR_ARG;
     }
-    if (p->n_clients < 1 || p->n_clients > 32 || p->n_ops < 1 || 2 * p->n_ops > QSMD_MAX_EVENTS) return QSMD_ERR_ARG;
-    if (p->lin_policy > 1 || p->pid_mode > 1) return QSMD_ERR_ARG;
-    if (!(p->p_bug >= 0.0 && p->p_bug <= 1.0)) return QSMD_ERR_ARG;       // (NaN fails both)
-    const uint32_t per = 2 * p->n_ops;
-    if ((uint64_t)ev_base + n_hist * (uint64_t)per > 0xFFFFFFFFull || n_hist > 0xFFFFFFFFull) return QSMD_ERR_ARG;
+    const qsmd_tgen::Sched sc{p->n_clients, p->n_ops, p->prefix_ops, p->lin_policy, p->pid_mode, p->overlap,
+                              p->p_bug, p->seed};
+    if (!qsmd_tgen::sched_ok(sc, n_hist, ev_base)) return QSMD_ERR_ARG;
     std::vector<uint32_t> weight(m.n_inv, 1u);
     if (p->inv_weight) std::copy(p->inv_weight, p->inv_weight + m.n_inv, weight.begin());
     uint64_t w_all = 0;
     for (uint32_t w : weight) w_all += w;
     if (w_all == 0 || w_all > 0xFFFFFFFFull) return QSMD_ERR_ARG;
 
-    const Gen g{*p, m, weight.data(), (uint32_t)w_all};
-    if (n_threads < 1) n_threads = 1;
-    auto work = [&](uint64_t lo, uint64_t hi) {
-        for (uint64_t i = lo; i < hi; ++i) {
-            qsmd_hdr& h = hdr[i];
-            std::memset(&h, 0, sizeof(h));
-            h.ev_off = ev_base + (uint32_t)(i * per);
-            h.n_ev = (uint16_t)per;
-            h.n_pid = (uint8_t)(p->pid_mode == QSMD_GEN_PID_SHARED ? 1 : p->n_clients);
-            h.model_id = (uint8_t)p->model_id;
-            h.tag = (uint32_t)(first + i);
-            g.one(first + i, events + i * per, bug_out ? bug_out + i : nullptr);
-        }
-    };
-    if (n_threads == 1 || n_hist < 1024) { work(0, n_hist); return 0; }
-    std::vector<std::thread> th;
-    const uint64_t chunk = (n_hist + n_threads - 1) / n_threads;
-    for (int t = 0; t < n_threads; ++t) {
-        const uint64_t lo = t * chunk, hi = std::min<uint64_t>(n_hist, lo + chunk);
-        if (lo >= hi) break;
-        th.emplace_back(work, lo, hi);
-    }
-    for (auto& x : th) x.join();
+    const Gen g{m, weight.data(), (uint32_t)w_all};
+    qsmd_tgen::gen_batch(sc, g, p->model_id, first, n_hist, ev_base, hdr, events, bug_out, n_threads);
     return 0;
 }

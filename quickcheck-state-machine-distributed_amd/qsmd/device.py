@@ -71,6 +71,7 @@ EXPORTS = {
     "qsmd_wellformed_batch_device": (_I, [_P, _P, _U64, _P, _U64, _P, _U32, _P, _P]),
     "qsmd_gen_batch_device": (_I, [_P, _P, _U64, _U64, _U32, _P, _P, _P, _P]),   # include/qsmd_gen.h
     "qsmd_gen_table_batch_device": (_I, [_P, _P, _U64, _U64, _U32, _P, _P, _P, _P]),
+    "qsmd_gen_ktable_batch_device": (_I, [_P, _P, _U64, _U64, _U32, _P, _P, _P, _P]),
     "qsmd_check_batch": (_I, [_P, _U32, _P, _U64, _P, _U64, _P, _U32, _U64, _P, _P, _P, _P]),
     "qsmd_check_batch_device": (_I, [_P, _U32, _P, _U64, _P, _U64, _P, _U32, _U64, _P, _P, _P, _P, _P]),
     "qsmd_last_kernel_ms": (_I, [_P, ctypes.POINTER(ctypes.c_float)]),
@@ -386,6 +387,27 @@ class Context:
         rc = self._lib.qsmd_gen_table_batch_device(self._h, ctypes.byref(params), first, n_hist, ev_base, hdr_ptr,
                                                    events_ptr, bug_ptr, stream)
         self._check(rc, "qsmd_gen_table_batch_device")
+
+    def gen_ktable_device(self, params, first, n_hist, hdr_ptr, events_ptr, bug_ptr=None, ev_base=0, stream=None):
+        """On-device generation from the context's keyed table (include/
+        qsmd_gen.h qsmd_gen_ktable_batch_device): the
+        qsmd.gen.generate_ktable stream [first, first + n_hist),
+        byte-identical to the host generator, into device buffers (async).
+        ``params``: a gen.KTableGenParams; an ``n_keys`` of 0 is set from the
+        keyed table set last (set_keyed_table), any other value must equal
+        the context's."""
+        held = self._keyed_table
+        if held is not None:
+            if params.n_keys == 0:
+                params.n_keys = held.n_keys
+            w, kw = getattr(params, "_weights", None), getattr(params, "_key_weights", None)
+            if w is not None and len(w) != len(held.component.invs):
+                raise ValueError(f"{len(w)} weights for a component of {len(held.component.invs)} invocation symbols")
+            if kw is not None and len(kw) != held.n_keys:
+                raise ValueError(f"{len(kw)} key weights for a keyed table of {held.n_keys} keys")
+        rc = self._lib.qsmd_gen_ktable_batch_device(self._h, ctypes.byref(params), first, n_hist, ev_base, hdr_ptr,
+                                                    events_ptr, bug_ptr, stream)
+        self._check(rc, "qsmd_gen_ktable_batch_device")
 
     def probe(self):
         """Routing of the most recent check call (qsmd_probe_read): histories

@@ -42,6 +42,16 @@ class TableGenParams(ctypes.Structure):
                 ("seed", ctypes.c_uint64), ("inv_weight", ctypes.c_void_p)]
 
 
+class KTableGenParams(ctypes.Structure):
+    """``qsmd_gen_ktable_params`` (include/qsmd_gen.h)."""
+    _fields_ = [("n_keys", ctypes.c_uint32), ("n_clients", ctypes.c_uint32),
+                ("n_ops", ctypes.c_uint32), ("prefix_ops", ctypes.c_uint32),
+                ("lin_policy", ctypes.c_uint32), ("pid_mode", ctypes.c_uint32),
+                ("overlap", ctypes.c_uint32), ("p_bug", ctypes.c_double),
+                ("seed", ctypes.c_uint64), ("inv_weight", ctypes.c_void_p),
+                ("key_weight", ctypes.c_void_p)]
+
+
 _lib = None
 
 
@@ -60,6 +70,11 @@ def _load():
                                            ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint32,
                                            ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                            ctypes.c_int]
+        L.qsmd_gen_ktable_batch.restype = ctypes.c_int
+        L.qsmd_gen_ktable_batch.argtypes = [ctypes.POINTER(KTableGenParams), ctypes.c_void_p,
+                                            ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint32,
+                                            ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                            ctypes.c_int]
         _lib = L
     return _lib
 
@@ -144,6 +159,55 @@ def generate_table(p, model, first, n_hist, threads=8, ev_base=0):
                                   hdr.ctypes.data, events.ctypes.data, flags.ctypes.data, threads)
     if rc != 0:
         raise ValueError(f"qsmd_gen_table_batch rejected the parameters ({rc})")
+    return hdr, events, flags
+
+
+def ktable_params(inv_weight=None, key_weight=None, **kw):
+    """A KTableGenParams.  ``inv_weight``: one weight per invocation symbol of
+    the component; ``key_weight``: one per key (None = every weight 1); a
+    pair's weight is their product.  The arrays are kept alive by the returned
+    structure.  ``n_keys`` is filled in from the model by generate_ktable, and
+    by Context.gen_ktable_device when it is 0."""
+    p = KTableGenParams()
+    for k, v in kw.items():
+        setattr(p, k, v)
+    if inv_weight is not None:
+        w = np.ascontiguousarray(inv_weight, dtype=np.uint32)
+        p._weights = w
+        p.inv_weight = w.ctypes.data
+    if key_weight is not None:
+        w = np.ascontiguousarray(key_weight, dtype=np.uint32)
+        p._key_weights = w
+        p.key_weight = w.ctypes.data
+    return p
+
+
+def _ktable_weights_fit(p, model):
+    w, kw = getattr(p, "_weights", None), getattr(p, "_key_weights", None)
+    if w is not None and len(w) != len(model.component.invs):
+        raise ValueError(f"{len(w)} weights for a component of {len(model.component.invs)} invocation symbols")
+    if kw is not None and len(kw) != model.n_keys:
+        raise ValueError(f"{len(kw)} key weights for a model of {model.n_keys} keys")
+
+
+def generate_ktable(p, model, first, n_hist, threads=8, ev_base=0):
+    """qsmd_gen_ktable_batch: (hdr, events, flags) numpy arrays for histories
+    [first, first + n_hist) of the stream ``p`` defines over ``model`` (a
+    models.KeyedTableModel; ``p.n_keys`` is set from it).  An invocation
+    event carries the component's symbol in ``code`` and its key in ``a``.
+    flags: bit 0 an injected bug, bit 1 a stuck step."""
+    lib = _load()
+    _ktable_weights_fit(p, model)
+    p.n_keys = model.n_keys
+    per = 2 * p.n_ops
+    hdr = np.zeros(n_hist, dtype=codec.HDR_DTYPE)
+    events = np.zeros(n_hist * per, dtype=codec.EV_DTYPE)
+    flags = np.zeros(n_hist, dtype=np.uint8)
+    st = model.component.c_struct()
+    rc = lib.qsmd_gen_ktable_batch(ctypes.byref(p), ctypes.addressof(st), first, n_hist, ev_base,
+                                   hdr.ctypes.data, events.ctypes.data, flags.ctypes.data, threads)
+    if rc != 0:
+        raise ValueError(f"qsmd_gen_ktable_batch rejected the parameters ({rc})")
     return hdr, events, flags
 
 

@@ -21,7 +21,7 @@ for p in "$@"; do
   patch -s -d "$SRC" -p0 < "$ROOT/$p"
 done
 objs=()
-for f in compact memo wave gen wellformed split table wtable tgen api; do
+for f in compact memo wave gen wellformed split table wtable ktable tgen ktgen api; do
   /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -w -I"$ROOT/include" -I"$SRC" $FLAGS \
     -c "$SRC/$f.hip" -o "$OUT/$f.o" &
   objs+=("$OUT/$f.o")

@@ -32,7 +32,11 @@ the register batch above as QSMD_MODEL_TABLE and as KeyedTableModel(register,
 4x16 histories of the register on K keys (tests/ktablegen.py's product
 generator) as QSMD_MODEL_KTABLE and, re-encoded, as QSMD_MODEL_WTABLE on the
 flat product (4^K states, 21 K invocations; K <= 4 tabulates in seconds),
-interleaved: what factoring buys.  Not with --generated, --wide or --model kv.
+interleaved: what factoring buys.  Not with --wide or --model kv.
+--keyed K --generated: the model-5 line alone, on --n DISTINCT keyed
+histories generated on the device (csrc/ktgen.hip, Context.gen_ktable_device)
+with --generated's settings, unit weights; --distinct D tiles the first D as
+above.  No flat product is tabulated, so any K in 1..8 runs.
 --memo sizes the keyed path's memo through its own knob ("ktable_memo") on
 the model-5 lines and "table_memo" on the others; every line carries the hits.
 
@@ -74,8 +78,8 @@ def main():
     ap.add_argument("--seed", type=int, default=0x7AB1E)
     ap.add_argument("--keyed", type=int, default=0)
     args = ap.parse_args()
-    if args.keyed and (args.generated or args.wide != "0" or args.model != "register"):
-        ap.error("--keyed runs the register model alone, from host-generated histories")
+    if args.keyed and (args.wide != "0" or args.model != "register"):
+        ap.error("--keyed runs the register model alone")
     tiled = args.distinct is not None or not args.generated
     if args.distinct is None:
         args.distinct = 65536 if tiled else args.n
@@ -101,7 +105,9 @@ def main():
         import ktablegen as kg
         km = KeyedTableModel(m, args.keyed)
         ctx.set_keyed_table(km)
-        if args.keyed == 1:
+        if args.generated:
+            ids, encoders = [5], {5: km}
+        elif args.keyed == 1:
             ids, encoders = [3, 5], {3: m, 5: km}
         else:
             model = kg.product(model, args.keyed)
@@ -114,13 +120,17 @@ def main():
     d_hdrs, d_evs = {}, {}
     if args.generated:
         per = 32
-        gp = gen.table_params(n_clients=4, n_ops=16, prefix_ops=0, lin_policy=gen.LIN_AT_INVOKE,
-                              pid_mode=gen.PID_PER_CLIENT, p_bug=0.39, seed=args.seed)
+        sched = dict(n_clients=4, n_ops=16, prefix_ops=0, lin_policy=gen.LIN_AT_INVOKE,
+                     pid_mode=gen.PID_PER_CLIENT, p_bug=0.39, seed=args.seed)
+        gp, kgp = gen.table_params(**sched), gen.ktable_params(**sched)
         d_ev = torch.empty(n * per * 8, dtype=torch.uint8, device=dev)
         for mid in ids:                     # the same stream from either table: only hdr.model_id differs
             h = torch.empty(n * 16, dtype=torch.uint8, device=dev)
-            ctx.gen_table_device(gp, 0, args.distinct, h.data_ptr(), d_ev.data_ptr(), None, stream=stream,
-                                 wide=mid == 4)
+            if mid == 5:
+                ctx.gen_ktable_device(kgp, 0, args.distinct, h.data_ptr(), d_ev.data_ptr(), None, stream=stream)
+            else:
+                ctx.gen_table_device(gp, 0, args.distinct, h.data_ptr(), d_ev.data_ptr(), None, stream=stream,
+                                     wide=mid == 4)
             torch.cuda.synchronize()
             if reps > 1:                    # tile on the device: ev_off moves on by one tile's events
                 first = h[:args.distinct * 16].view(torch.int32).view(args.distinct, 4)
@@ -133,7 +143,8 @@ def main():
             d_ev = d_ev[:args.distinct * per * 8].repeat(reps)
         d_evs[ids[0]] = d_ev
         n_events = n * per
-        what = (f"{args.model} 4x16 generated on the device (seed {args.seed:#x}, p_bug 0.39), " +
+        name = args.model + (f"^{args.keyed}" if args.keyed else "")
+        what = (f"{name} 4x16 generated on the device (seed {args.seed:#x}, p_bug 0.39), " +
                 (f"{args.distinct} distinct tiled to {n}" if reps > 1 else f"{n} distinct"))
     else:
         rng = random.Random("table_bench")

@@ -16,7 +16,13 @@ tests/wtablegen.py).  Per model, one JSON line:
            (pageable memory, wall clock with a device synchronisation): what a
            caller paid before the kernel existed.
 
-    python tools/tgen_bench.py [--n 1048576] [--models register,kv] [--threads 16] [--p-bug 0.0]
+--keyed K[,K...] adds, after the models' lines and in the same run, one line
+per K: the register on K keys (model 5) through the keyed launch
+(csrc/ktgen.hip, Context.gen_ktable_device), the host leg being
+qsmd.gen.generate_ktable.  "over_model3" is its median over the model-3
+register launch's of this run (when "register" is among --models).
+
+    python tools/tgen_bench.py [--n 1048576] [--models register,kv] [--keyed 1,4,8] [--threads 16] [--p-bug 0.0]
 """
 
 import argparse
@@ -33,13 +39,14 @@ for p in ("quickcheck-state-machine-distributed_amd", "oracle", "tests"):
 import tablegen as tg  # noqa: E402
 import wtablegen as wg  # noqa: E402
 from qsmd import device, gen  # noqa: E402
-from qsmd.models import TableModel  # noqa: E402
+from qsmd.models import KeyedTableModel, TableModel  # noqa: E402
 
 
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--n", type=int, default=1 << 20)
     ap.add_argument("--models", default="register,kv")
+    ap.add_argument("--keyed", default="", help="key counts for the keyed register lines, e.g. 1,4,8")
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--calls", type=int, default=20)
     ap.add_argument("--host-calls", type=int, default=3)
@@ -69,25 +76,41 @@ def main():
                 ms.append(e0.elapsed_time(e1))
         return ms
 
+    def register():
+        c = tg.REGISTER
+        return TableModel.from_closures(c["transition"], c["postcondition"], c["init"], c["invs"], c["resps"])
+
     ctx = device.Context(0)
-    for name in args.models.split(","):
-        if name == "kv":
-            m, wide = wg.wide_table("kv"), True
-            ctx.set_wide_table(m)
+    sched = dict(n_clients=4, n_ops=16, prefix_ops=4, lin_policy=args.lin, pid_mode=gen.PID_PER_CLIENT,
+                 p_bug=args.p_bug, seed=0x5EED)
+    runs = [(name, 0) for name in args.models.split(",") if name]
+    runs += [("register", int(k)) for k in args.keyed.split(",") if k]
+    model3_ms = None
+    for name, keys in runs:
+        if keys:
+            m = KeyedTableModel(register(), keys)
+            ctx.set_keyed_table(m)
+            p = gen.ktable_params(**sched)
+            launch = lambda: ctx.gen_ktable_device(p, 0, n, d_hdr.data_ptr(), d_ev.data_ptr(),  # noqa: E731
+                                                   d_fl.data_ptr(), stream=stream)
+            host = lambda: gen.generate_ktable(p, m, 0, n, threads=args.threads)  # noqa: E731
         else:
-            c = tg.REGISTER
-            m, wide = TableModel.from_closures(c["transition"], c["postcondition"], c["init"], c["invs"],
-                                               c["resps"]), False
-            ctx.set_table(m)
-        p = gen.table_params(n_clients=4, n_ops=16, prefix_ops=4, lin_policy=args.lin,
-                             pid_mode=gen.PID_PER_CLIENT, p_bug=args.p_bug, seed=0x5EED)
-        ms = timed(lambda: ctx.gen_table_device(p, 0, n, d_hdr.data_ptr(), d_ev.data_ptr(), d_fl.data_ptr(),
-                                                stream=stream, wide=wide))
+            if name == "kv":
+                m, wide = wg.wide_table("kv"), True
+                ctx.set_wide_table(m)
+            else:
+                m, wide = register(), False
+                ctx.set_table(m)
+            p = gen.table_params(**sched)
+            launch = lambda: ctx.gen_table_device(p, 0, n, d_hdr.data_ptr(), d_ev.data_ptr(),  # noqa: E731
+                                                  d_fl.data_ptr(), stream=stream, wide=wide)
+            host = lambda: gen.generate_table(p, m, 0, n, threads=args.threads)  # noqa: E731
+        ms = timed(launch)
         fill = timed(lambda: d_ev.fill_(0xA5))
         host_s, copy_s = [], []
         for _ in range(args.host_calls):
             t0 = time.perf_counter()
-            hdr, ev, fl = gen.generate_table(p, m, 0, n, threads=args.threads)
+            hdr, ev, fl = host()
             t1 = time.perf_counter()
             for a in (hdr, ev, fl):
                 torch.from_numpy(a.view("uint8")).to(dev)
@@ -98,8 +121,11 @@ def main():
         med, fmed = statistics.median(ms), statistics.median(fill)
         host_ms = statistics.median(host_s) * 1e3 if host_s else None      # --host-calls 0: the device alone
         copy_ms = statistics.median(copy_s) * 1e3 if copy_s else None
-        print(json.dumps({
-            "model": name, "model_id": m.model_id, "n": n, "n_inv": len(m.invs), "n_states": len(m.states),
+        if not keys and name == "register":
+            model3_ms = med
+        line = {
+            "model": f"{name}^{keys}" if keys else name, "model_id": m.model_id, "n": n, "n_inv": len(m.invs),
+            "n_states": len((m.component if keys else m).states),
             "workload": f"4x16 prefix 4, lin_policy {args.lin}, per-client pids, p_bug {args.p_bug}",
             "device_ms_median": round(med, 4), "device_ms_min": round(min(ms), 4), "device_ms_max": round(max(ms), 4),
             "histories_per_s": round(n / med * 1e3), "out_bytes": out_bytes,
@@ -108,7 +134,11 @@ def main():
             "host_threads": args.threads, "host_gen_ms_median": host_ms and round(host_ms, 2),
             "h2d_ms_median": copy_ms and round(copy_ms, 2),
             "host_total_over_device": host_ms and round((host_ms + copy_ms) / med, 1),
-        }), flush=True)
+        }
+        if keys:
+            line["keys"] = keys
+            line["over_model3"] = model3_ms and round(med / model3_ms, 3)
+        print(json.dumps(line), flush=True)
     ctx.close()
 
 
