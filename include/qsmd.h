@@ -250,7 +250,59 @@ typedef struct qsmd_wtable_model {
  *     "table_memo" has no effect on model 5, "ktable_memo" none on models 3
  *     and 4.
  * "table_budget" and "table_pass2_last" apply unchanged.  A context holds one
- * narrow, one wide and one keyed table, independently. */
+ * narrow, one wide and one keyed table, independently.
+ *
+ * Local mode -- knob "ktable_local" (qsmd_set_param / qsmd_get_param; default
+ * 0 = off: exactly the launches and results above; 1 = on; any other value
+ * QSMD_ERR_ARG and the old value stays).  Linearisability is local (Herlihy &
+ * Wing, Theorem 1): a complete, well-formed history over independent objects
+ * is linearisable exactly when each object's sub-history is.  With the knob at
+ * 1 a QSMD_MODEL_KTABLE call of qsmd_check_batch / qsmd_check_batch_device
+ * checks every *splittable* history key by key instead of on the product.  A
+ * call that carries QSMD_FLAG_WITNESS takes the product route whole, as if the
+ * knob were 0 (so does a call with more than (2^32-1) / n_keys histories);
+ * the knob has no effect on any other model.
+ *   - A history is splittable when (1) it is encode-valid by the rules above
+ *     (hdr.model_id == 5, n_ev <= 128, ev_off + n_ev <= n_events, every
+ *     invocation code < n_inv and a < n_keys, every response code < n_resp)
+ *     and (2) for every pid that occurs, the pid's events in history order
+ *     alternate invocation, response, invocation, response, ..., from an
+ *     invocation to a response: no pending invocation, no lone response, no
+ *     two invocations of one pid in flight.  An operation is then an
+ *     invocation and the next event of its pid, and a response belongs to its
+ *     invocation's key.
+ *   - Every other history is searched on the product, unchanged: its status
+ *     and nodes (an ENCODE_ERROR included) are those of the knob at 0.
+ *   - Sub-history k of a splittable history, for each key k in ascending
+ *     order: the events of the operations whose invocation has a == k, in
+ *     history order, bytes unchanged, the same header but for ev_off and n_ev,
+ *     the same model0 vector.  A key with no operation has none.  Each is
+ *     searched by the model-5 search above with the call's flags, max_nodes
+ *     (applied to each sub-search on its own), time limit, "table_budget" and
+ *     "ktable_memo".  Every sub-history is searched: no short cut across keys.
+ *   - The history's status is that of the lowest key whose sub-search is not
+ *     LINEARISABLE, or LINEARISABLE when there is none; its nodes is the sum
+ *     over its sub-searches; n_ev == 0 gives LINEARISABLE with 0 nodes.
+ *     qsmd_totals counts histories (nodes: the sum of the per-history values);
+ *     qsmd_timed_out, "table_pass2_last" and "table_memo_hits_last" describe
+ *     the launch over the sub-histories.
+ *   - "ktable_local_last" (qsmd_get_param; waits for the call): the histories
+ *     that were split in the most recent QSMD_MODEL_KTABLE call, 0 when it
+ *     took the product route.
+ *   - The call stays asynchronous on the caller's stream.  The sub-histories
+ *     are laid out in a copy of the events array, each history's inside its
+ *     own slot [ev_off, ev_off + n_ev): with the knob at 1 the slots of
+ *     different headers must not overlap.
+ * Promised: for a component without post_err, a splittable history's verdict
+ * (LINEARISABLE / NONLINEARISABLE) is the reference's on the product model
+ * whenever neither side ends in BUDGET.  With post_err, LINEARISABLE still
+ * means that every key's sub-history is linearisable, and the rule above
+ * holds.  Not promised: the node counts are not the reference's on the
+ * product -- they are the reference's on each key, summed; BUDGET is per key
+ * (a history the product search leaves BUDGET is usually decided); and with
+ * post_err a failing history may read NONLINEARISABLE where the product search
+ * reads MODEL_ERROR, or the reverse (when the reference raises depends on the
+ * order of its branches). */
 #define QSMD_MODEL_KTABLE 5u
 #define QSMD_KTABLE_MAX_KEYS 8
 

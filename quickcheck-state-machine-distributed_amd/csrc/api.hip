@@ -207,6 +207,13 @@ struct qsmd_ctx {
     uint32_t ktab_keys = 0;
     uint64_t ktable_memo = 0;
     uint32_t tm_epoch_k = 0;
+    // its local mode (csrc/ksplit.hip, knob "ktable_local"; 0 = off: the
+    // product search): the sub-headers, the events grouped by key and the
+    // sub-searches' results, in a workspace of its own
+    uint64_t ktable_local = 0;
+    bool ktable_local_call = false;    // the most recent model-5 call took the local route
+    char* kl = nullptr;
+    size_t kl_bytes = 0;
     uint8_t* wf_rank_host = nullptr;   // wellformed: pid rank table (pinned) and its device copy
     char* wf_rank_dev = nullptr;
     size_t wf_rank_bytes = 0;
@@ -399,12 +406,12 @@ int qsmd_open(qsmd_ctx** out, int device) {
     hipDeviceProp_t prop;
     if (hipGetDeviceProperties(&prop, device) == hipSuccess) c->n_cu = prop.multiProcessorCount;
     if (hipEventCreateWithFlags(&c->done_ev, hipEventDisableTiming) != hipSuccess ||
-        hipHostMalloc(reinterpret_cast<void**>(&c->probe_host), 64,
+        hipHostMalloc(reinterpret_cast<void**>(&c->probe_host), kProbeWords * 4,
                       hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess) {
         qsmd_close(c);
         return QSMD_ERR_DEVICE;
     }
-    std::memset(c->probe_host, 0, 64);
+    std::memset(c->probe_host, 0, kProbeWords * 4);
     *out = c;
     return QSMD_OK;
 }
@@ -421,6 +428,7 @@ void qsmd_close(qsmd_ctx* c) {
     if (c->ktab_blob) (void)hipFree(c->ktab_blob);
     if (c->tws) (void)hipFree(c->tws);
     if (c->tm) (void)hipFree(c->tm);
+    if (c->kl) (void)hipFree(c->kl);
     if (c->mt) (void)hipFree(c->mt);
     if (c->rs) (void)hipFree(c->rs);
     if (c->xm) (void)hipFree(c->xm);
@@ -545,6 +553,9 @@ int qsmd_set_param(qsmd_ctx* c, const char* name, uint64_t value) {
         if (!ktable_memo_ok(value))
             return fail(c, QSMD_ERR_ARG, "ktable_memo: 0 (off) or a power of two in 2..2^20");
         c->ktable_memo = value;
+    } else if (n == "ktable_local") {       // QSMD_MODEL_KTABLE: each key searched on its own (csrc/ksplit.hip)
+        if (value > 1) return fail(c, QSMD_ERR_ARG, "ktable_local: 0 (the product search) or 1");
+        c->ktable_local = value;
     } else if (n == "table_memo_grid") {    // diagnostic: pass 2's workgroups at most with the memo (0 = automatic)
         if (value > 65536) return fail(c, QSMD_ERR_ARG, "table_memo_grid in 0..65536");
         c->table_memo_grid = value;
@@ -884,6 +895,62 @@ static int check_table_locked(qsmd_ctx* c, const qsmd_hdr* hdr, uint64_t n_hist,
     HIP_TRY(c, hipSetDevice(c->device), "hipSetDevice");
     HIP_TRY(c, order_after_previous(c, s), "order after the previous call");
 
+    // The keyed model's local mode ("ktable_local", csrc/ksplit.hip): the
+    // split kernel writes n_keys sub-headers per history and the events
+    // grouped by key into c->kl, the launches below search the sub-headers as
+    // an ordinary model-5 batch (every width class: a history's parts are
+    // narrower than it) into c->kl, and the combine kernels fold the parts'
+    // results into the caller's outputs -- one stream, no host round trip.  A
+    // call with a witness, or one whose sub-headers would pass 2^32-1, takes
+    // the product route whole.
+    KSplitArgs ks{};
+    bool local = false;
+    if constexpr (KEYED) {
+        local = c->ktable_local != 0 && !(flags & QSMD_FLAG_WITNESS) &&
+                n_hist * (uint64_t)c->ktab_keys <= 0xFFFFFFFFull;
+        c->ktable_local_call = local;
+        if (local) {
+            const uint64_t n_sub = n_hist * c->ktab_keys;
+            const size_t o_bk = 256;
+            const size_t o_tot = o_bk + (size_t)kBuckets * kBucketWords * 8;
+            const size_t o_hdr = o_tot + align_up(sizeof(qsmd_totals));
+            const size_t o_ev = o_hdr + align_up(n_sub * sizeof(qsmd_hdr));
+            const size_t o_nd = o_ev + align_up(n_events * sizeof(qsmd_event));
+            const size_t o_st = o_nd + align_up(n_sub * 8);
+            int rc = grow(c, &c->kl, &c->kl_bytes, o_st + align_up(n_sub));
+            if (rc) return rc;
+            HIP_TRY(c, hipMemsetAsync(c->kl, 0, o_tot, s), "memset local header");
+            ks.hdr = hdr;
+            ks.events = reinterpret_cast<const uint2*>(events);
+            ks.n_hist = n_hist;
+            ks.n_events = n_events;
+            ks.n_keys = c->ktab_keys;
+            ks.n_inv = c->ktab.n_inv;
+            ks.n_resp = c->ktab.n_resp;
+            ks.sub_hdr = reinterpret_cast<qsmd_hdr*>(c->kl + o_hdr);
+            ks.sub_events = reinterpret_cast<uint2*>(c->kl + o_ev);
+            ks.sub_status = reinterpret_cast<uint8_t*>(c->kl + o_st);
+            ks.sub_nodes = reinterpret_cast<uint64_t*>(c->kl + o_nd);
+            ks.status = status;
+            ks.nodes = nodes;
+            ks.totals = totals ? totals : reinterpret_cast<qsmd_totals*>(c->kl + o_tot);
+            ks.buckets = reinterpret_cast<unsigned long long*>(c->kl + o_bk);
+            ks.n_split = reinterpret_cast<uint32_t*>(c->kl);
+            ks.probe_host = c->probe_host;
+            const uint32_t grid = (uint32_t)std::min<uint64_t>(std::max<uint64_t>(n_hist, 1), 32ull * c->n_cu);
+            HIP_TRY(c, launch_ksplit(ks, grid, s), "split launch");
+            // from here on the call is the search of the parts; its totals
+            // stay in the workspace
+            hdr = ks.sub_hdr;
+            n_hist = n_sub;
+            events = reinterpret_cast<const qsmd_event*>(ks.sub_events);
+            status = const_cast<uint8_t*>(ks.sub_status);
+            nodes = const_cast<uint64_t*>(ks.sub_nodes);
+            totals = reinterpret_cast<qsmd_totals*>(c->kl + o_tot);
+            route = 0u;
+        }
+    }
+
     const size_t lst = align_up(n_hist * 4 + 4);
     const size_t off_tot = kTabHeader + 6 * lst;
     int rc = grow(c, &c->tws, &c->tws_bytes, off_tot + align_up(sizeof(qsmd_totals)));
@@ -995,6 +1062,7 @@ static int check_table_locked(qsmd_ctx* c, const qsmd_hdr* hdr, uint64_t n_hist,
         for (int k = 0; k < 3; ++k) grid2[k] = (uint32_t)gm;
     }
     HIP_TRY(c, launch_table(p, grid1, grid2, (route & kClassesKnown) ? (route & 7u) : 7u, s), "table launch");
+    if (local) HIP_TRY(c, launch_kcombine(ks, s), "combine launch");
     const bool own = s == c->stream;
     if (!own) HIP_TRY(c, hipEventRecord(c->done_ev, s), "hipEventRecord");
     c->done_last = !own;
@@ -1815,6 +1883,11 @@ int qsmd_get_param(qsmd_ctx* c, const char* name, uint64_t* out) {
         *out = c->table_memo;
     } else if (n == "ktable_memo") {
         *out = c->ktable_memo;
+    } else if (n == "ktable_local") {
+        *out = c->ktable_local;
+    } else if (n == "ktable_local_last") {   // histories split in the most recent QSMD_MODEL_KTABLE call
+        quiesce(c);
+        *out = c->ktable_local_call ? c->probe_host[kProbeKLocal] : 0u;
     } else if (n == "table_memo_grid") {
         *out = c->table_memo_grid;
     } else if (n == "table_memo_hits_last") {   // memo hits of the most recent QSMD_MODEL_TABLE call

@@ -493,6 +493,34 @@ struct KTableArgs {
 hipError_t launch_table(const KTableArgs& p, const uint32_t grid1[3], const uint32_t grid2[3], uint32_t classes,
                         hipStream_t s);
 
+// QSMD_MODEL_KTABLE's local mode (csrc/ksplit.hip, knob "ktable_local"): the
+// split kernel writes n_keys sub-headers per history (slot h * n_keys + k) and
+// the events grouped by key into the context's workspace, launch_table
+// searches the sub-headers as an ordinary model-5 batch into sub_status /
+// sub_nodes, and the combine kernels fold those into the caller's outputs.
+constexpr int kProbeKLocal = 16;        // probe_host: histories split in the most recent local call
+constexpr int kProbeWords = 32;         // qsmd_ctx::probe_host, in 32-bit words
+struct KSplitArgs {
+    const qsmd_hdr* hdr;          // the caller's
+    const uint2* events;
+    uint64_t n_hist;
+    uint64_t n_events;
+    uint32_t n_keys, n_inv, n_resp;
+    qsmd_hdr* sub_hdr;            // [n_hist * n_keys]
+    uint2* sub_events;            // [n_events]
+    const uint8_t* sub_status;    // [n_hist * n_keys]
+    const uint64_t* sub_nodes;
+    uint8_t* status;              // the caller's outputs
+    uint64_t* nodes;              // may be null
+    qsmd_totals* totals;          // device
+    unsigned long long* buckets;  // [kBuckets][kBucketWords], zeroed per call
+    uint32_t* n_split;            // device counter, zeroed per call
+    uint32_t* probe_host;         // pinned
+};
+hipError_t launch_ksplit(const KSplitArgs& p, uint32_t grid, hipStream_t s);
+// combine + totals and the split count (after launch_table on the same stream)
+hipError_t launch_kcombine(const KSplitArgs& p, hipStream_t s);
+
 // Early exit: relaxed agent-scope read (a stale value only delays skipping).
 __device__ __forceinline__ bool beyond_first_fail(const SearchArgs& a, uint32_t h) {
     return a.first_fail && h > __hip_atomic_load(a.first_fail, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);

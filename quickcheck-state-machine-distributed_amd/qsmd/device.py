@@ -274,6 +274,12 @@ class Context:
         QSMD_MODEL_WTABLE or QSMD_MODEL_KTABLE call (qsmd_get_param "table_pass2_last")."""
         return self.get_param("table_pass2_last")
 
+    def ktable_local_last(self):
+        """Histories that were split by key in the most recent
+        QSMD_MODEL_KTABLE call (knob "ktable_local"; 0 when the call searched
+        the product; qsmd_get_param "ktable_local_last")."""
+        return self.get_param("ktable_local_last")
+
     def table_memo_hits(self):
         """Hits of the second pass's state memo (knob "table_memo"; for a
         QSMD_MODEL_KTABLE call "ktable_memo") in the most recent table call

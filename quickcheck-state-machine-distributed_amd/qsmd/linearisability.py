@@ -94,12 +94,16 @@ class CheckResult:
 
 
 def linearisable_batch(model, histories, model0=None, *, max_nodes=0, witness=False,
-                       flags=device.QSMD_FLAG_EXHAUSTIVE, ctx=None, table_memo=None) -> CheckResult:
+                       flags=device.QSMD_FLAG_EXHAUSTIVE, ctx=None, table_memo=None,
+                       ktable_local=None) -> CheckResult:
     """Check many histories in one device call.  ``table_memo`` (table models:
     entries per lane slot of the second pass's state memo, 0 = off) sets the
     context's "table_memo" knob for this call and restores it afterwards;
     with a :class:`KeyedTableModel` the knob is the keyed path's own,
-    "ktable_memo"."""
+    "ktable_memo".  ``ktable_local`` (a :class:`KeyedTableModel` only): None
+    leaves the context's "ktable_local" knob alone, True / False set it for
+    this call in the same way -- every splittable history is then checked key
+    by key (include/qsmd.h; :meth:`KeyedTableModel.split_history`)."""
     m = _as_model(model)
     batch = codec.encode(m, histories, model0)
     accounts0 = m.new_account_map(model0)
@@ -118,20 +122,28 @@ def linearisable_batch(model, histories, model0=None, *, max_nodes=0, witness=Fa
     if table_memo is not None:
         saved = ctx.get_param(knob)
         ctx.set_param(knob, table_memo)
+    saved_local = None
+    if ktable_local is not None and isinstance(m, KeyedTableModel):
+        saved_local = ctx.get_param("ktable_local")
+        ctx.set_param("ktable_local", 1 if ktable_local else 0)
     try:
         status, nodes, wit, totals = ctx.check_arrays(m.model_id, batch.hdr, batch.events, packed,
                                                       flags, max_nodes, witness)
     finally:
         if saved is not None:
             ctx.set_param(knob, saved)
+        if saved_local is not None:
+            ctx.set_param("ktable_local", saved_local)
     return CheckResult(batch, status, nodes, wit, totals)
 
 
-def linearisable(transition, postcondition, model0, history, *, max_nodes=0, ctx=None, table_memo=None) -> bool:
+def linearisable(transition, postcondition, model0, history, *, max_nodes=0, ctx=None, table_memo=None,
+                 ktable_local=None) -> bool:
     """``linearisable`` (src/Linearisability.hs:52-69) on the GPU
-    (``table_memo``: see :func:`linearisable_batch`)."""
+    (``table_memo``, ``ktable_local``: see :func:`linearisable_batch`)."""
     m = _device_model(transition, postcondition)
-    res = linearisable_batch(m, [history], model0, max_nodes=max_nodes, ctx=ctx, table_memo=table_memo)
+    res = linearisable_batch(m, [history], model0, max_nodes=max_nodes, ctx=ctx, table_memo=table_memo,
+                             ktable_local=ktable_local)
     st = int(res.status[0])
     if st == codec.STATUS_LIN:
         return True

@@ -646,6 +646,45 @@ class KeyedTableModel(DeviceModel):
             return None
         return (ctypes.c_uint32 * self.n_keys)(*[self.component._state(s) for s in self._model(model0)])
 
+    def split_history(self, history):
+        """The per-key sub-histories the local mode searches (knob
+        "ktable_local", include/qsmd.h): ``None`` when ``history`` is not
+        *splittable*, else ``[(key, sub_history), ...]`` in ascending key
+        order, keys with no operation left out.
+
+        Splittable: at most 128 events, every invocation a ``(key, inv)`` of
+        this model and every response one of the component's, and every pid's
+        events alternating invocation, response, ... from an invocation to a
+        response (no pending invocation, no lone response, no two operations
+        of one pid in flight).  An operation is an invocation and its pid's
+        next event; sub-history ``k`` is the events, unchanged and in history
+        order, of the operations invoked on key ``k``."""
+        history = list(history)
+        if len(history) > 128:
+            return None
+        open_key = {}                   # pid -> the key of its operation in flight
+        parts = {}
+        for pid, (kind, x) in history:
+            try:
+                if kind == "L":
+                    k = self.encode_inv(x, None)[1]
+                else:
+                    self.encode_resp(x)
+            except EncodeError:
+                return None
+            if kind == "L":
+                if pid in open_key:
+                    return None
+                open_key[pid] = k
+            else:
+                if pid not in open_key:
+                    return None
+                k = open_key.pop(pid)
+            parts.setdefault(k, []).append((pid, (kind, x)))
+        if open_key:
+            return None
+        return sorted(parts.items())
+
     def show_model(self, model):
         return "{" + ", ".join(f"{k}: {self.component.show_model(s)}" for k, s in enumerate(model)) + "}"
 

@@ -39,9 +39,16 @@ with --generated's settings, unit weights; --distinct D tiles the first D as
 above.  No flat product is tabulated, so any K in 1..8 runs.
 --memo sizes the keyed path's memo through its own knob ("ktable_memo") on
 the model-5 lines and "table_memo" on the others; every line carries the hits.
+--local 0,1 (with --keyed): the model-5 lines with the keyed path's local mode
+off and on (knob "ktable_local", csrc/ksplit.hip: every splittable history
+checked key by key), crossed with the budgets and memo sizes; a line carries
+"ktable_local" and the histories that were split.  --clients C --ops K --p-bug P
+shape the --generated batch (default 4, 16 and 0.39: P is the probability that
+a history gets its one response bug, 1 - 0.97^K for 3 % per operation).
 
     python tools/table_bench.py [--budgets default,0] [--memo 0,64,256,1024,4096] [--distinct 65536] [--n 1048576]
                                 [--wide 0|1|both] [--model register|kv] [--generated] [--seed S] [--keyed K]
+                                [--local 0,1] [--clients C] [--ops K] [--p-bug P]
 """
 
 import argparse
@@ -77,7 +84,15 @@ def main():
     ap.add_argument("--generated", action="store_true")
     ap.add_argument("--seed", type=int, default=0x7AB1E)
     ap.add_argument("--keyed", type=int, default=0)
+    ap.add_argument("--local", default="0")
+    ap.add_argument("--clients", type=int, default=4)
+    ap.add_argument("--ops", type=int, default=16)
+    ap.add_argument("--p-bug", type=float, default=0.39)
     args = ap.parse_args()
+    if args.local != "0" and not args.keyed:
+        ap.error("--local is the keyed path's (--keyed K)")
+    if (args.clients, args.ops, args.p_bug) != (4, 16, 0.39) and not args.generated:
+        ap.error("--clients / --ops / --p-bug shape the --generated batch")
     if args.keyed and (args.wide != "0" or args.model != "register"):
         ap.error("--keyed runs the register model alone")
     tiled = args.distinct is not None or not args.generated
@@ -119,9 +134,9 @@ def main():
     n = reps * args.distinct
     d_hdrs, d_evs = {}, {}
     if args.generated:
-        per = 32
-        sched = dict(n_clients=4, n_ops=16, prefix_ops=0, lin_policy=gen.LIN_AT_INVOKE,
-                     pid_mode=gen.PID_PER_CLIENT, p_bug=0.39, seed=args.seed)
+        per = 2 * args.ops
+        sched = dict(n_clients=args.clients, n_ops=args.ops, prefix_ops=0, lin_policy=gen.LIN_AT_INVOKE,
+                     pid_mode=gen.PID_PER_CLIENT, p_bug=args.p_bug, seed=args.seed)
         gp, kgp = gen.table_params(**sched), gen.ktable_params(**sched)
         d_ev = torch.empty(n * per * 8, dtype=torch.uint8, device=dev)
         for mid in ids:                     # the same stream from either table: only hdr.model_id differs
@@ -144,7 +159,7 @@ def main():
         d_evs[ids[0]] = d_ev
         n_events = n * per
         name = args.model + (f"^{args.keyed}" if args.keyed else "")
-        what = (f"{name} 4x16 generated on the device (seed {args.seed:#x}, p_bug 0.39), " +
+        what = (f"{name} {args.clients}x{args.ops} generated on the device (seed {args.seed:#x}, p_bug {args.p_bug}), " +
                 (f"{args.distinct} distinct tiled to {n}" if reps > 1 else f"{n} distinct"))
     else:
         rng = random.Random("table_bench")
@@ -169,15 +184,16 @@ def main():
     d_nd = torch.empty(n, dtype=torch.int64, device=dev)
     d_tot = torch.zeros(8, dtype=torch.int64, device=dev)
     default = ctx.get_param("table_budget")
-    cross = [(b, int(e), mid) for _ in range(args.rounds) for b in args.budgets.split(",")
-             for e in args.memo.split(",") for mid in ids]
-    for b, entries, mid in cross:
+    cross = [(b, int(e), mid, int(loc)) for _ in range(args.rounds) for b in args.budgets.split(",")
+             for e in args.memo.split(",") for mid in ids for loc in (args.local.split(",") if mid == 5 else "0")]
+    for b, entries, mid, local in cross:
         d_hdr, d_ev = d_hdrs[mid], d_evs.get(mid, next(iter(d_evs.values())))
         budget = default if b == "default" else int(b)
         ctx.set_param("table_budget", budget)
         # (the keyed path's memo has its own knob; each knob is set for its own path alone)
         ctx.set_param("table_memo", 0 if mid == 5 else entries)
         ctx.set_param("ktable_memo", entries if mid == 5 else 0)
+        ctx.set_param("ktable_local", local)
         ms = []
         for k in range(args.warmup + args.calls):
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -195,6 +211,7 @@ def main():
             "workload": what,
             "table_budget": budget, "is_default": budget == default, "table_memo": entries,
             "memo_knob": "ktable_memo" if mid == 5 else "table_memo", "table_memo_hits": ctx.table_memo_hits(), "calls": args.calls,
+            "ktable_local": local, "ktable_local_last": ctx.ktable_local_last() if mid == 5 else 0,
             "ms_per_call_median": round(med, 4), "ms_min": round(min(ms), 4), "ms_max": round(max(ms), 4),
             "histories_per_s": round(n / med * 1e3), "nodes_per_s": round(int(tot[7]) / med * 1e3),
             "nodes_per_call": int(tot[7]), "pass2_histories": ctx.table_pass2(),
