@@ -424,6 +424,74 @@ int qsmd_check_batch_device(qsmd_ctx* ctx, uint32_t model_id,
                             uint8_t* witness_dev, qsmd_totals* totals_dev,
                             void* stream);
 
+/* ----------------------------------------------------------------- explain
+ * Where a history went wrong: the deepest linearised path of its search, for
+ * the table models (QSMD_MODEL_TABLE, QSMD_MODEL_WTABLE, QSMD_MODEL_KTABLE).
+ *
+ * qsmd_explain_batch runs the search of qsmd_check_batch -- the same flags
+ * (QSMD_FLAG_EXHAUSTIVE), max_nodes, time limit and "table_budget" passes --
+ * and reports status and nodes exactly as qsmd_check_batch without a memo
+ * does.  A *node at depth d* is a step whose postcondition held, so that the
+ * search recurses; d counts the operations on the stack, that node included.
+ * Per history one path is reported in the witness layout: path_out[ev_off + k]
+ * is the history-local index of the invocation event chosen at depth k, and
+ * the list ends at QSMD_WITNESS_END when it is shorter than n_ev.
+ *
+ *   LINEARISABLE     the witness; the state at its end
+ *   NONLINEARISABLE, the path to the first node of maximal depth in DFS order
+ *   BUDGET           among the nodes counted before the search ended (by
+ *                    exhaustion, max_nodes or the time limit); the state after
+ *                    that node's operation.  Depth 0: no first operation
+ *                    passed (the state is the initial one)
+ *   MODEL_ERROR      the search's current path when the postcondition raised,
+ *                    i.e. the path to the parent of the raising step; the
+ *                    state at its end
+ *   ENCODE_ERROR     the path bytes as the caller gave them, except that a
+ *                    slot with n_ev >= 1 and ev_off < n_events has its first
+ *                    byte set to QSMD_WITNESS_END; the record all zero
+ *
+ * n_ev == 0 is LINEARISABLE with depth 0 at the initial state (no byte
+ * written).
+ *
+ * Limits.  The explanation is always the plain search, for model 5 on the
+ * product: the knobs "table_memo", "ktable_memo" and "ktable_local" are
+ * ignored by these two calls (a folded subtree has no path to report), so a
+ * history whose plain search passes max_nodes reads BUDGET, with the deepest
+ * path seen so far, even where the memo would have let a check call decide it.
+ * "table_budget" applies; pass 2 starts again from the root, and so does the
+ * record.  qsmd_timed_out and "table_pass2_last" describe the call as they do
+ * for a check.  The cascade models (1, 2) return QSMD_ERR_UNSUPPORTED, and so
+ * does QSMD_FLAG_EARLY_EXIT_BATCH; QSMD_FLAG_WITNESS and QSMD_FLAG_MEMO are
+ * accepted and change nothing.  The model0 rules, "no table set" and the
+ * n_hist limits are those of the check call.  nodes_out and totals_out may be
+ * NULL; path_out (n_events bytes) and explain_out (n_hist records) may not. */
+typedef struct qsmd_explain {
+    uint16_t depth;      /* operations on the reported path                          */
+    uint16_t reserved;   /* 0                                                        */
+    uint32_t reserved2;  /* 0                                                        */
+    uint64_t state;      /* model state at its end: models 3 / 4 the state index;    */
+                         /* model 5 key k's component state in bits 8k .. 8k + 7     */
+} qsmd_explain;          /* 16 bytes */
+
+/* Host memory, synchronous (as qsmd_check_batch). */
+int qsmd_explain_batch(qsmd_ctx* ctx, uint32_t model_id,
+                       const qsmd_hdr* hdr, uint64_t n_hist,
+                       const qsmd_event* events, uint64_t n_events,
+                       const void* model0, uint32_t flags, uint64_t max_nodes,
+                       uint8_t* status_out, uint64_t* nodes_out,
+                       uint8_t* path_out, qsmd_explain* explain_out,
+                       qsmd_totals* totals_out);
+
+/* Device memory, asynchronous on `stream` (as qsmd_check_batch_device). */
+int qsmd_explain_batch_device(qsmd_ctx* ctx, uint32_t model_id,
+                              const qsmd_hdr* hdr_dev, uint64_t n_hist,
+                              const qsmd_event* events_dev, uint64_t n_events,
+                              const void* model0_host, uint32_t flags,
+                              uint64_t max_nodes,
+                              uint8_t* status_dev, uint64_t* nodes_dev,
+                              uint8_t* path_dev, qsmd_explain* explain_dev,
+                              qsmd_totals* totals_dev, void* stream);
+
 /* Safety net: a search launch whose lanes run longer than this wall time
  * stops and reports QSMD_STATUS_BUDGET for the unfinished histories (default
  * 120000 ms; 0 disables).  Not part of the reference semantics. */

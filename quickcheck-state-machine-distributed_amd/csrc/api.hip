@@ -869,8 +869,12 @@ template <int KIND>
 static int check_table_locked(qsmd_ctx* c, const qsmd_hdr* hdr, uint64_t n_hist, const qsmd_event* events,
                               uint64_t n_events, const void* model0, uint32_t flags, uint64_t max_nodes,
                               uint8_t* status, uint64_t* nodes, uint8_t* witness, qsmd_totals* totals,
-                              hipStream_t s, uint32_t route) {
+                              hipStream_t s, uint32_t route, uint8_t* path = nullptr,
+                              qsmd_explain* explain = nullptr) {
     constexpr bool WIDE = KIND == kTabWide, KEYED = KIND == kTabKeyed;
+    // explain != null: a qsmd_explain_batch call -- the same launches with the
+    // EXPLAIN instantiations, always the plain search on the product (no
+    // memo, no local mode, no witness: the path is the witness)
     if (flags & QSMD_FLAG_EARLY_EXIT_BATCH)
         return fail(c, QSMD_ERR_UNSUPPORTED, "QSMD_FLAG_EARLY_EXIT_BATCH: not for the table models");
     if constexpr (WIDE) {
@@ -906,7 +910,7 @@ static int check_table_locked(qsmd_ctx* c, const qsmd_hdr* hdr, uint64_t n_hist,
     KSplitArgs ks{};
     bool local = false;
     if constexpr (KEYED) {
-        local = c->ktable_local != 0 && !(flags & QSMD_FLAG_WITNESS) &&
+        local = c->ktable_local != 0 && !explain && !(flags & QSMD_FLAG_WITNESS) &&
                 n_hist * (uint64_t)c->ktab_keys <= 0xFFFFFFFFull;
         c->ktable_local_call = local;
         if (local) {
@@ -967,7 +971,9 @@ static int check_table_locked(qsmd_ctx* c, const qsmd_hdr* hdr, uint64_t n_hist,
     p.s.time_limit = c->time_limit_ms * 100000ull;   // 100 MHz s_memrealtime
     p.s.status = status;
     p.s.nodes = nodes;
-    p.s.witness = (flags & QSMD_FLAG_WITNESS) ? witness : nullptr;
+    p.s.witness = (flags & QSMD_FLAG_WITNESS) && !explain ? witness : nullptr;
+    p.path = path;
+    p.explain = reinterpret_cast<uint4*>(explain);
     p.s.buckets = reinterpret_cast<unsigned long long*>(c->tws + kTabOffBuckets);
     p.cnt = reinterpret_cast<uint32_t*>(c->tws);
     p.s.timed_out = p.cnt + TC_TIMED;
@@ -1014,7 +1020,7 @@ static int check_table_locked(qsmd_ctx* c, const qsmd_hdr* hdr, uint64_t n_hist,
     // ("ktable_memo"; "table_memo" does not reach it, nor "ktable_memo" the
     // other two), 48-byte entries and full-word epochs; its sizing is
     // ktable_memo_plan (ktable_host.h).
-    const uint64_t memo_entries = KEYED ? c->ktable_memo : c->table_memo;
+    const uint64_t memo_entries = explain ? 0 : (KEYED ? c->ktable_memo : c->table_memo);
     if (memo_entries && c->table_budget) {
         uint64_t gm;
         size_t need;
@@ -1061,7 +1067,13 @@ static int check_table_locked(qsmd_ctx* c, const qsmd_hdr* hdr, uint64_t n_hist,
         p.memo_epoch = epoch & kEpochMask;
         for (int k = 0; k < 3; ++k) grid2[k] = (uint32_t)gm;
     }
-    HIP_TRY(c, launch_table(p, grid1, grid2, (route & kClassesKnown) ? (route & 7u) : 7u, s), "table launch");
+    const uint32_t classes = (route & kClassesKnown) ? (route & 7u) : 7u;
+    if (explain) {
+        HIP_TRY(c, launch_explain_prepare(p.s, (uint64_t)state0, path, p.explain, s), "explain prepare launch");
+        HIP_TRY(c, launch_table_explain(p, grid1, grid2, classes, s), "table explain launch");
+    } else {
+        HIP_TRY(c, launch_table(p, grid1, grid2, classes, s), "table launch");
+    }
     if (local) HIP_TRY(c, launch_kcombine(ks, s), "combine launch");
     const bool own = s == c->stream;
     if (!own) HIP_TRY(c, hipEventRecord(c->done_ev, s), "hipEventRecord");
@@ -1573,6 +1585,97 @@ int qsmd_check_batch(qsmd_ctx* c, uint32_t model_id, const qsmd_hdr* hdr, uint64
     if (n_hist && nodes_out) std::memcpy(nodes_out, host + o_nd, n_hist * 8);
     if (want_w) std::memcpy(witness_out, host + o_w, n_events);
     if (totals_out) std::memcpy(totals_out, host + o_tot, sizeof(qsmd_totals));
+    return QSMD_OK;
+}
+
+// qsmd_explain_batch's route: the table models only, through
+// check_table_locked with the explain outputs.
+static int explain_device_locked(qsmd_ctx* c, uint32_t model_id, const qsmd_hdr* hdr, uint64_t n_hist,
+                                 const qsmd_event* events, uint64_t n_events, const void* model0, uint32_t flags,
+                                 uint64_t max_nodes, uint8_t* status, uint64_t* nodes, uint8_t* path,
+                                 qsmd_explain* explain, qsmd_totals* totals, hipStream_t s, uint32_t route) {
+    if (model_id == QSMD_MODEL_BANK || model_id == QSMD_MODEL_TICKET)
+        return fail(c, QSMD_ERR_UNSUPPORTED, "qsmd_explain_batch: the table models only (3, 4, 5)");
+    if (model_id != QSMD_MODEL_TABLE && model_id != QSMD_MODEL_WTABLE && model_id != QSMD_MODEL_KTABLE)
+        return fail(c, QSMD_ERR_ARG, "unknown model_id");
+    if (flags & QSMD_FLAG_EARLY_EXIT_BATCH)
+        return fail(c, QSMD_ERR_UNSUPPORTED, "QSMD_FLAG_EARLY_EXIT_BATCH: not for the table models");
+    if (n_hist && (!path || !explain)) return fail(c, QSMD_ERR_ARG, "null path/explain");
+    static qsmd_explain none;          // n_hist == 0: no record is written; the route needs a non-null pointer
+    if (!explain) explain = &none;
+    if (model_id == QSMD_MODEL_KTABLE)
+        return check_table_locked<kTabKeyed>(c, hdr, n_hist, events, n_events, model0, flags, max_nodes, status,
+                                             nodes, nullptr, totals, s, route, path, explain);
+    if (model_id == QSMD_MODEL_WTABLE)
+        return check_table_locked<kTabWide>(c, hdr, n_hist, events, n_events, model0, flags, max_nodes, status,
+                                            nodes, nullptr, totals, s, route, path, explain);
+    return check_table_locked<kTabNarrow>(c, hdr, n_hist, events, n_events, model0, flags, max_nodes, status, nodes,
+                                          nullptr, totals, s, route, path, explain);
+}
+
+int qsmd_explain_batch_device(qsmd_ctx* c, uint32_t model_id, const qsmd_hdr* hdr_dev, uint64_t n_hist,
+                              const qsmd_event* events_dev, uint64_t n_events, const void* model0_host,
+                              uint32_t flags, uint64_t max_nodes, uint8_t* status_dev, uint64_t* nodes_dev,
+                              uint8_t* path_dev, qsmd_explain* explain_dev, qsmd_totals* totals_dev, void* stream) {
+    if (!c) return QSMD_ERR_ARG;
+    std::lock_guard<std::mutex> g(c->mu);
+    hipStream_t s = stream ? static_cast<hipStream_t>(stream) : ctx_stream(c);
+    if (!s) return fail(c, QSMD_ERR_DEVICE, "hipStreamCreate");
+    return explain_device_locked(c, model_id, hdr_dev, n_hist, events_dev, n_events, model0_host, flags, max_nodes,
+                                 status_dev, nodes_dev, path_dev, explain_dev, totals_dev, s, 0u);
+}
+
+int qsmd_explain_batch(qsmd_ctx* c, uint32_t model_id, const qsmd_hdr* hdr, uint64_t n_hist,
+                       const qsmd_event* events, uint64_t n_events, const void* model0, uint32_t flags,
+                       uint64_t max_nodes, uint8_t* status_out, uint64_t* nodes_out, uint8_t* path_out,
+                       qsmd_explain* explain_out, qsmd_totals* totals_out) {
+    if (!c) return QSMD_ERR_ARG;
+    if (n_hist && (!hdr || !status_out)) return fail(c, QSMD_ERR_ARG, "null hdr/status");
+    if (n_events && !events) return fail(c, QSMD_ERR_ARG, "null events");
+    if (n_hist && (!path_out || !explain_out)) return fail(c, QSMD_ERR_ARG, "null path/explain");
+    std::lock_guard<std::mutex> g(c->mu);
+    HIP_TRY(c, hipSetDevice(c->device), "hipSetDevice");
+    hipStream_t s = ctx_stream(c);
+    if (!s) return fail(c, QSMD_ERR_DEVICE, "hipStreamCreate");
+    HIP_TRY(c, order_after_previous(c, s), "order after the previous call");
+    // io layout: [hdr | events | path] copied in (the caller's path bytes: an
+    // ENCODE_ERROR slot keeps them), [path | status | nodes | explain | totals] copied out
+    const size_t o_hdr = 0;
+    const size_t o_ev = o_hdr + align_up(n_hist * sizeof(qsmd_hdr), 16);
+    const size_t o_p = o_ev + align_up(n_events * sizeof(qsmd_event), 16);
+    const size_t o_st = o_p + align_up(n_events, 16);
+    const size_t o_nd = o_st + align_up(n_hist, 16);
+    const size_t o_x = o_nd + align_up(n_hist * 8, 16);
+    const size_t o_tot = o_x + align_up(n_hist * sizeof(qsmd_explain), 16);
+    const size_t need = o_tot + align_up(sizeof(qsmd_totals), 16);
+    int rc = grow(c, &c->io, &c->io_bytes, need);
+    if (rc) return rc;
+    rc = grow_pinned(c, need);
+    if (rc) return rc;
+    if (n_hist) std::memcpy(c->pin + o_hdr, hdr, n_hist * sizeof(qsmd_hdr));
+    if (n_events) std::memcpy(c->pin + o_ev, events, n_events * sizeof(qsmd_event));
+    if (n_events) std::memcpy(c->pin + o_p, path_out, n_events);
+    if (o_st) HIP_TRY(c, hipMemcpyAsync(c->io, c->pin, o_st, hipMemcpyHostToDevice, s), "H2D inputs");
+    uint32_t route = kClassesKnown;         // the width classes present (one launch per non-empty class)
+    for (uint64_t i = 0; i < n_hist && (route & 7u) != 7u; ++i)
+        route |= hdr[i].n_ev <= 32u ? 1u : (hdr[i].n_ev <= 64u ? 2u : 4u);
+    rc = explain_device_locked(c, model_id, reinterpret_cast<qsmd_hdr*>(c->io + o_hdr), n_hist,
+                               reinterpret_cast<qsmd_event*>(c->io + o_ev), n_events, model0, flags, max_nodes,
+                               reinterpret_cast<uint8_t*>(c->io + o_st), reinterpret_cast<uint64_t*>(c->io + o_nd),
+                               reinterpret_cast<uint8_t*>(c->io + o_p), reinterpret_cast<qsmd_explain*>(c->io + o_x),
+                               reinterpret_cast<qsmd_totals*>(c->io + o_tot), s, route);
+    if (rc) {
+        (void)hipStreamSynchronize(s);      // (the copy in may still read the pinned buffer)
+        return rc;
+    }
+    HIP_TRY(c, hipMemcpyAsync(c->pin + o_p, c->io + o_p, need - o_p, hipMemcpyDeviceToHost, s), "D2H outputs");
+    HIP_TRY(c, hipStreamSynchronize(s), "hipStreamSynchronize");
+    c->in_flight = false;
+    if (n_hist) std::memcpy(status_out, c->pin + o_st, n_hist);
+    if (n_hist && nodes_out) std::memcpy(nodes_out, c->pin + o_nd, n_hist * 8);
+    if (n_events) std::memcpy(path_out, c->pin + o_p, n_events);
+    if (n_hist) std::memcpy(explain_out, c->pin + o_x, n_hist * sizeof(qsmd_explain));
+    if (totals_out) std::memcpy(totals_out, c->pin + o_tot, sizeof(qsmd_totals));
     return QSMD_OK;
 }
 

@@ -420,6 +420,8 @@ struct TableArgs {
                                   // entries of 2 x uint4, or null (off: today's launches)
     uint32_t memo_entries;        // a power of two
     uint32_t memo_epoch;          // this call's tag (24 bits)
+    uint8_t* path;                // the explain call's outputs (launch_table_explain), else null:
+    uint4* explain;               // the witness layout; one qsmd_explain (16 B) per history
 };
 // bin + per class pass 1 (+ pass 2 when budget) + finish; grid1 / grid2: the
 // workgroups of each class's passes (any value >= 1 gives the same results);
@@ -429,6 +431,18 @@ hipError_t launch_table(const TableArgs& p, const uint32_t grid1[3], const uint3
 // the LDS bytes of one workgroup of class k (0, 1, 2)
 // (memo: pass 2 with the state memo, + 8 B per level and lane)
 size_t table_lds_bytes(const TableDev& t, int k, bool memo = false);
+
+// The explain calls (qsmd_explain_batch): launch_table with the EXPLAIN
+// instantiations of the search kernels, which also write p.path and
+// p.explain for every history they decide.  launch_explain_prepare goes first
+// on the stream: the records of what the binning kernel decides from the
+// header alone (ENCODE_ERROR: zero; n_ev == 0: depth 0 at state0) and the
+// terminator of a header-level ENCODE_ERROR whose slot starts inside the
+// events array.
+hipError_t launch_explain_prepare(const SearchArgs& a, uint64_t state0, uint8_t* path, uint4* explain,
+                                  hipStream_t s);
+hipError_t launch_table_explain(const TableArgs& p, const uint32_t grid1[3], const uint32_t grid2[3],
+                                uint32_t classes, hipStream_t s);
 
 // QSMD_MODEL_WTABLE (csrc/wtable.hip): the same search for up to 65,536
 // states and 256 symbols; the tables stay in device memory.  The context's
@@ -463,9 +477,13 @@ struct WTableArgs {
     uint4* memo;
     uint32_t memo_entries;
     uint32_t memo_epoch;
+    uint8_t* path;                // the explain call's outputs (launch_table_explain), else null:
+    uint4* explain;               // the witness layout; one qsmd_explain (16 B) per history
 };
 hipError_t launch_table(const WTableArgs& p, const uint32_t grid1[3], const uint32_t grid2[3], uint32_t classes,
                         hipStream_t s);
+hipError_t launch_table_explain(const WTableArgs& p, const uint32_t grid1[3], const uint32_t grid2[3],
+                                uint32_t classes, hipStream_t s);
 
 // QSMD_MODEL_KTABLE (csrc/ktable.hip): the product of n_keys copies of one
 // narrow component table, searched exactly.  `t` is the component's blob (the
@@ -489,9 +507,13 @@ struct KTableArgs {
                                   // entries of 3 x uint4, or null (off: the plain pass 2)
     uint32_t memo_entries;        // a power of two
     uint32_t memo_epoch;          // this call's tag: a full word, never 0
+    uint8_t* path;                // the explain call's outputs (launch_table_explain), else null:
+    uint4* explain;               // the witness layout; one qsmd_explain (16 B) per history
 };
 hipError_t launch_table(const KTableArgs& p, const uint32_t grid1[3], const uint32_t grid2[3], uint32_t classes,
                         hipStream_t s);
+hipError_t launch_table_explain(const KTableArgs& p, const uint32_t grid1[3], const uint32_t grid2[3],
+                                uint32_t classes, hipStream_t s);
 
 // QSMD_MODEL_KTABLE's local mode (csrc/ksplit.hip, knob "ktable_local"): the
 // split kernel writes n_keys sub-headers per history (slot h * n_keys + k) and

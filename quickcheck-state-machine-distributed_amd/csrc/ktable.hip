@@ -175,15 +175,19 @@ struct KTableDFS {
     // MEMO (pass 2 with "ktable_memo"): a subtree left by a backtrack is
     // recorded with the nodes it counted, a descent into a recorded (rem,
     // state) counts them and backtracks at once.
-    template <bool MEMO>
+    // EXPLAIN (the explain calls, never with MEMO): xp records the deepest
+    // path into `path` (DeepPath, table_lane.h).
+    template <bool MEMO, bool EXPLAIN>
     __device__ __forceinline__ int step(const TableDev& t, const KTabLds& L, const uint16_t* ev, uint16_t* stk,
-                                        int lane, uint64_t limit, KTableMemo<M>& mm) {
+                                        int lane, uint64_t limit, KTableMemo<M>& mm, DeepPath<uint64_t>& xp,
+                                        uint8_t* path) {
         const bool empty = !MO::any(cand);
         if (empty && (found == 0u || depth == 0u)) return kTerm;
         if (empty) {
             // backtrack: the parent's remaining set by Lemma L1, the one
             // component the step changed from the stack
             --depth;
+            if constexpr (EXPLAIN) xp.fell_to(depth);
             if constexpr (MEMO) {
                 // (rem, state) are still the node's being left
                 if (!mm.skip) mm.record(rem, state, nodes - mm.entry[depth * C_LANES]);
@@ -224,6 +228,8 @@ struct KTableDFS {
             rem = rem & ~(MO::lowest(rem & pmj & INV) | MO::bit((int)r));
             cand = t_cands(rem, INV, RESP);
             found = 0u;
+            if constexpr (EXPLAIN)
+                xp.descended(path, depth, state, [&](uint32_t d) { return stk[col16(d, lane)] & 0xFFu; });
             if constexpr (MEMO) {
                 mm.entry[(depth - 1u) * C_LANES] = nodes;
                 uint64_t c;
@@ -325,7 +331,7 @@ __global__ __launch_bounds__(C_LANES) void ktable_bin(KTableArgs a) {
 // heavy list, every search to its end.
 // MEMO: pass 2 with the state memo (a.memo: one table of a.memo_entries
 // entries per lane slot of the grid).
-template <class M, bool MEMO>
+template <class M, bool MEMO, bool EXPLAIN>
 __global__ __launch_bounds__(C_LANES) void ktable_search(KTableArgs a, uint32_t pass2) {
     constexpr int EV = TW<M>::EV, K = TW<M>::CLASS;
     extern __shared__ uint32_t lds[];
@@ -382,11 +388,14 @@ __global__ __launch_bounds__(C_LANES) void ktable_search(KTableArgs a, uint32_t 
             if (status == -1) dfs.init(a.state0);
         }
         if constexpr (MEMO) mm.begin(h);
+        DeepPath<uint64_t> xp;
+        if constexpr (EXPLAIN) xp.begin(H.ev_off, a.state0);
         // the search, the time limit checked every 1024 iterations (a
         // wavefront-uniform counter: the loop runs while any lane searches)
         while (__ballot(status == -1) != 0ull) {
             for (uint32_t k = 0; k < 1024u; ++k) {
-                if (status == -1) status = dfs.template step<MEMO>(a.t, L, ev, stk, lane, limit, mm);
+                if (status == -1)
+                    status = dfs.template step<MEMO, EXPLAIN>(a.t, L, ev, stk, lane, limit, mm, xp, a.path);
                 if (__ballot(status == -1) == 0ull) break;
             }
             if (status == -1 && a.s.time_limit && __builtin_amdgcn_s_memrealtime() - t0 > a.s.time_limit) {
@@ -407,6 +416,10 @@ __global__ __launch_bounds__(C_LANES) void ktable_search(KTableArgs a, uint32_t 
                 for (uint32_t d = 0; d < dfs.depth; ++d) w[d] = (uint8_t)(stk[col16(d, lane)] & 0xFFu);
                 if (dfs.depth < H.n_ev) w[dfs.depth] = QSMD_WITNESS_END;
             }
+        }
+        if constexpr (EXPLAIN) {
+            const auto at = [&](uint32_t d) { return stk[col16(d, lane)] & 0xFFu; };
+            if (out) xp.finish(a.path, status, H.n_ev, dfs.depth, dfs.state, at, a.explain + h);
         }
         cnt.add(out, status, dfs.nodes);
         if constexpr (MEMO) {
@@ -439,15 +452,16 @@ __global__ __launch_bounds__(C_LANES) void ktable_finish(KTableArgs a) {
     }
 }
 
-template <class M, bool MEMO>
+template <class M, bool MEMO, bool EXPLAIN = false>
 hipError_t launch_class(const KTableArgs& p, uint32_t grid, uint32_t pass2, hipStream_t s) {
     const size_t lds = table_lds_bytes(p.t, TW<M>::CLASS, MEMO);
     if (lds > 64u * 1024u) {
         static std::atomic<int> set[kAttrDevices];
-        const hipError_t e = ensure_dyn_lds(reinterpret_cast<const void*>(&ktable_search<M, MEMO>), set, lds);
+        const hipError_t e =
+            ensure_dyn_lds(reinterpret_cast<const void*>(&ktable_search<M, MEMO, EXPLAIN>), set, lds);
         if (e != hipSuccess) return e;
     }
-    hipLaunchKernelGGL((ktable_search<M, MEMO>), dim3(grid), dim3(C_LANES), lds, s, p, pass2);
+    hipLaunchKernelGGL((ktable_search<M, MEMO, EXPLAIN>), dim3(grid), dim3(C_LANES), lds, s, p, pass2);
     return hipGetLastError();
 }
 
@@ -469,6 +483,25 @@ hipError_t launch_table(const KTableArgs& p, const uint32_t grid1[3], const uint
         if (e == hipSuccess && (classes & 1u)) e = launch_class<uint32_t, false>(p, g[0], pass2, s);
         if (e == hipSuccess && (classes & 2u)) e = launch_class<uint64_t, false>(p, g[1], pass2, s);
         if (e == hipSuccess && (classes & 4u)) e = launch_class<M128, false>(p, g[2], pass2, s);
+    }
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(ktable_finish, dim3(1), dim3(C_LANES), 0, s, p);
+    return hipGetLastError();
+}
+
+// The explain call's launches (include/qsmd.h qsmd_explain_batch): launch_table
+// with the EXPLAIN instantiations, always the plain search (p.memo null); the
+// caller has run launch_explain_prepare on the stream.
+hipError_t launch_table_explain(const KTableArgs& p, const uint32_t grid1[3], const uint32_t grid2[3], uint32_t classes,
+                                hipStream_t s) {
+    const uint32_t gb = (uint32_t)std::min<uint64_t>(std::max<uint64_t>((p.s.n_hist + 63) / 64, 1), 4096);
+    hipLaunchKernelGGL(ktable_bin, dim3(gb), dim3(C_LANES), 0, s, p);
+    hipError_t e = hipGetLastError();
+    for (uint32_t pass2 = 0; pass2 < (p.budget ? 2u : 1u) && e == hipSuccess; ++pass2) {
+        const uint32_t* g = pass2 ? grid2 : grid1;
+        if (e == hipSuccess && (classes & 1u)) e = launch_class<uint32_t, false, true>(p, g[0], pass2, s);
+        if (e == hipSuccess && (classes & 2u)) e = launch_class<uint64_t, false, true>(p, g[1], pass2, s);
+        if (e == hipSuccess && (classes & 4u)) e = launch_class<M128, false, true>(p, g[2], pass2, s);
     }
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(ktable_finish, dim3(1), dim3(C_LANES), 0, s, p);

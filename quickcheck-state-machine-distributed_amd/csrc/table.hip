@@ -98,9 +98,12 @@ struct TableDFS {
     // MEMO (pass 2 with "table_memo"): a subtree left by a backtrack is
     // recorded with the nodes it counted, a descent into a recorded state
     // counts them and backtracks at once (the rule of memo.hip's memo_step).
-    template <bool MEMO>
+    // EXPLAIN (the explain calls, never with MEMO): xp records the deepest
+    // path into `path` (DeepPath, table_lane.h).
+    template <bool MEMO, bool EXPLAIN>
     __device__ __forceinline__ int step(const TableDev& t, const TabLds& L, const uint16_t* ev, uint16_t* stk,
-                                        int lane, uint64_t limit, TableMemo<M>& mm) {
+                                        int lane, uint64_t limit, TableMemo<M>& mm, DeepPath<uint32_t>& xp,
+                                        uint8_t* path) {
         const bool empty = !MO::any(cand);
         // no children: a leaf => True (any' []), the root => False (any [])
         if (empty && (found == 0u || depth == 0u)) return kTerm;
@@ -108,6 +111,7 @@ struct TableDFS {
             // backtrack: the parent's remaining set by Lemma L1, its state
             // from the stack
             --depth;
+            if constexpr (EXPLAIN) xp.fell_to(depth);
             if constexpr (MEMO) {
                 // (rem, state) are still the node's being left
                 if (!mm.skip) mm.record(rem, state, nodes - mm.entry[depth * C_LANES]);
@@ -144,6 +148,8 @@ struct TableDFS {
             rem = rem & ~(MO::lowest(rem & pmj & INV) | MO::bit((int)r));
             cand = t_cands(rem, INV, RESP);
             found = 0u;
+            if constexpr (EXPLAIN)
+                xp.descended(path, depth, state, [&](uint32_t d) { return stk[col16(d, lane)] & 0xFFu; });
             if constexpr (MEMO) {
                 mm.entry[(depth - 1u) * C_LANES] = nodes;
                 uint64_t c;
@@ -196,7 +202,7 @@ __global__ __launch_bounds__(C_LANES) void table_bin(TableArgs a) {
 // heavy list, every search to its end.
 // MEMO: pass 2 with the state memo (a.memo: one table of a.memo_entries
 // entries per lane slot of the grid).
-template <class M, bool MEMO>
+template <class M, bool MEMO, bool EXPLAIN>
 __global__ __launch_bounds__(C_LANES) void table_search(TableArgs a, uint32_t pass2) {
     constexpr int EV = TW<M>::EV, K = TW<M>::CLASS;
     extern __shared__ uint32_t lds[];
@@ -253,11 +259,14 @@ __global__ __launch_bounds__(C_LANES) void table_search(TableArgs a, uint32_t pa
             if (status == -1) dfs.init(a.state0);
         }
         if constexpr (MEMO) mm.begin(h);
+        DeepPath<uint32_t> xp;
+        if constexpr (EXPLAIN) xp.begin(H.ev_off, a.state0);
         // the search, the time limit checked every 1024 iterations (a
         // wavefront-uniform counter: the loop runs while any lane searches)
         while (__ballot(status == -1) != 0ull) {
             for (uint32_t k = 0; k < 1024u; ++k) {
-                if (status == -1) status = dfs.template step<MEMO>(a.t, L, ev, stk, lane, limit, mm);
+                if (status == -1)
+                    status = dfs.template step<MEMO, EXPLAIN>(a.t, L, ev, stk, lane, limit, mm, xp, a.path);
                 if (__ballot(status == -1) == 0ull) break;
             }
             if (status == -1 && a.s.time_limit && __builtin_amdgcn_s_memrealtime() - t0 > a.s.time_limit) {
@@ -278,6 +287,10 @@ __global__ __launch_bounds__(C_LANES) void table_search(TableArgs a, uint32_t pa
                 for (uint32_t d = 0; d < dfs.depth; ++d) w[d] = (uint8_t)(stk[col16(d, lane)] & 0xFFu);
                 if (dfs.depth < H.n_ev) w[dfs.depth] = QSMD_WITNESS_END;
             }
+        }
+        if constexpr (EXPLAIN) {
+            const auto at = [&](uint32_t d) { return stk[col16(d, lane)] & 0xFFu; };
+            if (out) xp.finish(a.path, status, H.n_ev, dfs.depth, dfs.state, at, a.explain + h);
         }
         cnt.add(out, status, dfs.nodes);
         if constexpr (MEMO) {
@@ -310,15 +323,34 @@ __global__ __launch_bounds__(C_LANES) void table_finish(TableArgs a) {
     }
 }
 
-template <class M, bool MEMO>
+// The explain call's first launch, for the three table models (a.model_id):
+// every history's qsmd_explain record as the binning kernel's verdicts need it
+// -- zero, with the initial state for an empty history (depth 0); the search
+// kernels overwrite the records of the histories they decide -- and, for an
+// ENCODE_ERROR found in the header, the terminator in the first byte of a slot
+// that has one inside the events array.
+__global__ __launch_bounds__(C_LANES) void explain_prepare(SearchArgs a, uint64_t state0, uint8_t* path,
+                                                           uint4* explain) {
+    for (uint64_t h = (uint64_t)blockIdx.x * C_LANES + threadIdx.x; h < a.n_hist; h += (uint64_t)gridDim.x * C_LANES) {
+        const qsmd_hdr H = a.hdr[h];
+        const bool enc_ok = H.model_id == a.model_id && H.n_ev <= QSMD_MAX_EVENTS &&
+                            (uint64_t)H.ev_off + H.n_ev <= a.n_events;
+        const uint64_t st = enc_ok ? state0 : 0ull;     // (enc_ok and searched: overwritten)
+        explain[h] = make_uint4(0u, 0u, (uint32_t)st, (uint32_t)(st >> 32));
+        if (!enc_ok && H.n_ev > 0u && (uint64_t)H.ev_off < a.n_events) path[H.ev_off] = QSMD_WITNESS_END;
+    }
+}
+
+template <class M, bool MEMO, bool EXPLAIN = false>
 hipError_t launch_class(const TableArgs& p, uint32_t grid, uint32_t pass2, hipStream_t s) {
     const size_t lds = table_lds_bytes(p.t, TW<M>::CLASS, MEMO);
     if (lds > 64u * 1024u) {
         static std::atomic<int> set[kAttrDevices];
-        const hipError_t e = ensure_dyn_lds(reinterpret_cast<const void*>(&table_search<M, MEMO>), set, lds);
+        const hipError_t e =
+            ensure_dyn_lds(reinterpret_cast<const void*>(&table_search<M, MEMO, EXPLAIN>), set, lds);
         if (e != hipSuccess) return e;
     }
-    hipLaunchKernelGGL((table_search<M, MEMO>), dim3(grid), dim3(C_LANES), lds, s, p, pass2);
+    hipLaunchKernelGGL((table_search<M, MEMO, EXPLAIN>), dim3(grid), dim3(C_LANES), lds, s, p, pass2);
     return hipGetLastError();
 }
 
@@ -327,6 +359,13 @@ hipError_t launch_class(const TableArgs& p, uint32_t grid, uint32_t pass2, hipSt
 size_t table_lds_bytes(const TableDev& t, int k, bool memo) {
     const size_t ev = k == 0 ? 32 : (k == 1 ? 64 : 128);
     return ((ev / 2 + ev / 4 + (memo ? ev : 0)) * C_LANES + (size_t)t.blob_words) * 4;
+}
+
+hipError_t launch_explain_prepare(const SearchArgs& a, uint64_t state0, uint8_t* path, uint4* explain,
+                                  hipStream_t s) {
+    const uint32_t gb = (uint32_t)std::min<uint64_t>(std::max<uint64_t>((a.n_hist + 63) / 64, 1), 4096);
+    hipLaunchKernelGGL(explain_prepare, dim3(gb), dim3(C_LANES), 0, s, a, state0, path, explain);
+    return hipGetLastError();
 }
 
 hipError_t launch_table(const TableArgs& p, const uint32_t grid1[3], const uint32_t grid2[3], uint32_t classes,
@@ -346,6 +385,25 @@ hipError_t launch_table(const TableArgs& p, const uint32_t grid1[3], const uint3
         if (e == hipSuccess && (classes & 1u)) e = launch_class<uint32_t, false>(p, g[0], pass2, s);
         if (e == hipSuccess && (classes & 2u)) e = launch_class<uint64_t, false>(p, g[1], pass2, s);
         if (e == hipSuccess && (classes & 4u)) e = launch_class<M128, false>(p, g[2], pass2, s);
+    }
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(table_finish, dim3(1), dim3(C_LANES), 0, s, p);
+    return hipGetLastError();
+}
+
+// The explain call's launches (include/qsmd.h qsmd_explain_batch): launch_table
+// with the EXPLAIN instantiations, always the plain search (p.memo null); the
+// caller has run launch_explain_prepare on the stream.
+hipError_t launch_table_explain(const TableArgs& p, const uint32_t grid1[3], const uint32_t grid2[3], uint32_t classes,
+                                hipStream_t s) {
+    const uint32_t gb = (uint32_t)std::min<uint64_t>(std::max<uint64_t>((p.s.n_hist + 63) / 64, 1), 4096);
+    hipLaunchKernelGGL(table_bin, dim3(gb), dim3(C_LANES), 0, s, p);
+    hipError_t e = hipGetLastError();
+    for (uint32_t pass2 = 0; pass2 < (p.budget ? 2u : 1u) && e == hipSuccess; ++pass2) {
+        const uint32_t* g = pass2 ? grid2 : grid1;
+        if (e == hipSuccess && (classes & 1u)) e = launch_class<uint32_t, false, true>(p, g[0], pass2, s);
+        if (e == hipSuccess && (classes & 2u)) e = launch_class<uint64_t, false, true>(p, g[1], pass2, s);
+        if (e == hipSuccess && (classes & 4u)) e = launch_class<M128, false, true>(p, g[2], pass2, s);
     }
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(table_finish, dim3(1), dim3(C_LANES), 0, s, p);

@@ -114,6 +114,63 @@ struct TableMemo {
     }
 };
 
+// One lane's record of the deepest path of its search (the explain calls,
+// include/qsmd.h qsmd_explain_batch; the EXPLAIN instantiations of the three
+// steps).  `best` is the depth of the first node of maximal depth so far,
+// `state` the model state after that node's operation (S: uint32_t, keyed
+// uint64_t), `common` the lowest depth the stack has fallen back to since the
+// last record: the path bytes below it are still the stack's.  A descent that
+// passes `best` stores the stack's chosen events of levels [common, depth) --
+// at most once per operation of the history, so the divergent byte stores are
+// rare and the step pays one compare per descent.  at(d): the chosen event of
+// stack level d.
+template <class S>
+struct DeepPath {
+    uint32_t off;           // the history's slot in the path array: ev_off (the base pointer is uniform)
+    uint32_t best, common;
+    S state;
+
+    __device__ __forceinline__ void begin(uint32_t ev_off, S state0) {
+        off = ev_off;
+        best = 0u;
+        common = 0u;
+        state = state0;
+    }
+    __device__ __forceinline__ void fell_to(uint32_t depth) { common = min(common, depth); }
+    template <class At>
+    __device__ __forceinline__ void descended(uint8_t* base, uint32_t depth, S now, At at) {
+        if (depth > best) {
+            uint8_t* path = base + off;
+            for (uint32_t d = common; d < depth; ++d) path[d] = (uint8_t)at(d);
+            best = depth;
+            common = depth;
+            state = now;
+        }
+    }
+    // The end of a search: LINEARISABLE and MODEL_ERROR report the current
+    // stack (depth, now), the others the record; then the terminator and the
+    // qsmd_explain record (depth 16 | 0 16, 0, state lo, state hi).  An
+    // ENCODE_ERROR found while staging: the terminator first, the record zero.
+    template <class At>
+    __device__ __forceinline__ void finish(uint8_t* base, int status, uint32_t n_ev, uint32_t depth, S now, At at,
+                                           uint4* rec) {
+        uint8_t* path = base + off;
+        if (status == QSMD_STATUS_ENCODE_ERROR) {
+            path[0] = QSMD_WITNESS_END;
+            *rec = make_uint4(0u, 0u, 0u, 0u);
+            return;
+        }
+        if (status == QSMD_STATUS_LINEARISABLE || status == QSMD_STATUS_MODEL_ERROR) {
+            for (uint32_t d = 0; d < depth; ++d) path[d] = (uint8_t)at(d);
+            best = depth;
+            state = now;
+        }
+        if (best < n_ev) path[best] = QSMD_WITNESS_END;
+        const uint64_t st = (uint64_t)state;
+        *rec = make_uint4(best, 0u, (uint32_t)st, (uint32_t)(st >> 32));
+    }
+};
+
 // The lane stages its own history: 8 loads in flight (the index clamped into
 // the history), the 16-bit events into its LDS column, the kind and the seven
 // pid bits into mask planes one 32-bit word at a time.  Returns false for an

@@ -69,13 +69,17 @@ struct WTableDFS {
     // One iteration: TableDFS::step with the tables in device memory and the
     // 32-bit stack.  Returns -1 = go on, kTerm, QSMD_STATUS_BUDGET or
     // QSMD_STATUS_MODEL_ERROR.
-    template <bool MEMO>
+    // EXPLAIN (the explain calls, never with MEMO): xp records the deepest
+    // path into `path` (DeepPath, table_lane.h).
+    template <bool MEMO, bool EXPLAIN>
     __device__ __forceinline__ int step(const WTableDev& t, const uint16_t* on_resp, const uint16_t* ev,
-                                        uint32_t* stk, int lane, uint64_t limit, TableMemo<M>& mm) {
+                                        uint32_t* stk, int lane, uint64_t limit, TableMemo<M>& mm,
+                                        DeepPath<uint32_t>& xp, uint8_t* path) {
         const bool empty = !MO::any(cand);
         if (empty && (found == 0u || depth == 0u)) return kTerm;
         if (empty) {
             --depth;
+            if constexpr (EXPLAIN) xp.fell_to(depth);
             if constexpr (MEMO) {
                 if (!mm.skip) mm.record(rem, state, nodes - mm.entry[depth * C_LANES]);
                 mm.skip = false;
@@ -114,6 +118,8 @@ struct WTableDFS {
             rem = rem & ~(MO::lowest(rem & pmj & INV) | MO::bit((int)r));
             cand = t_cands(rem, INV, RESP);
             found = 0u;
+            if constexpr (EXPLAIN)
+                xp.descended(path, depth, state, [&](uint32_t d) { return stk[d * C_LANES + lane] & 0xFFu; });
             if constexpr (MEMO) {
                 mm.entry[(depth - 1u) * C_LANES] = nodes;
                 uint64_t c;
@@ -164,7 +170,7 @@ __global__ __launch_bounds__(C_LANES) void wtable_bin(WTableArgs a) {
 // table.hip's table_search: PASS2 false = the class list with the pass-1
 // budget, true = the class's heavy list to the end; MEMO = pass 2 with the
 // state memo.
-template <class M, bool MEMO>
+template <class M, bool MEMO, bool EXPLAIN>
 __global__ __launch_bounds__(C_LANES) void wtable_search(WTableArgs a, uint32_t pass2) {
     constexpr int EV = TW<M>::EV, K = TW<M>::CLASS;
     extern __shared__ uint32_t lds[];
@@ -210,11 +216,14 @@ __global__ __launch_bounds__(C_LANES) void wtable_search(WTableArgs a, uint32_t 
             if (status == -1) dfs.init(a.state0);
         }
         if constexpr (MEMO) mm.begin(h);
+        DeepPath<uint32_t> xp;
+        if constexpr (EXPLAIN) xp.begin(H.ev_off, a.state0);
         // the search, the time limit checked every 1024 iterations (a
         // wavefront-uniform counter: the loop runs while any lane searches)
         while (__ballot(status == -1) != 0ull) {
             for (uint32_t k = 0; k < 1024u; ++k) {
-                if (status == -1) status = dfs.template step<MEMO>(a.t, on_resp, ev, stk, lane, limit, mm);
+                if (status == -1)
+                    status = dfs.template step<MEMO, EXPLAIN>(a.t, on_resp, ev, stk, lane, limit, mm, xp, a.path);
                 if (__ballot(status == -1) == 0ull) break;
             }
             if (status == -1 && a.s.time_limit && __builtin_amdgcn_s_memrealtime() - t0 > a.s.time_limit) {
@@ -235,6 +244,10 @@ __global__ __launch_bounds__(C_LANES) void wtable_search(WTableArgs a, uint32_t 
                 for (uint32_t d = 0; d < dfs.depth; ++d) w[d] = (uint8_t)(stk[d * C_LANES + lane] & 0xFFu);
                 if (dfs.depth < H.n_ev) w[dfs.depth] = QSMD_WITNESS_END;
             }
+        }
+        if constexpr (EXPLAIN) {
+            const auto at = [&](uint32_t d) { return stk[d * C_LANES + lane] & 0xFFu; };
+            if (out) xp.finish(a.path, status, H.n_ev, dfs.depth, dfs.state, at, a.explain + h);
         }
         cnt.add(out, status, dfs.nodes);
         if constexpr (MEMO) {
@@ -269,11 +282,11 @@ __global__ __launch_bounds__(C_LANES) void wtable_finish(WTableArgs a) {
 }
 
 // (at most 64 KB, the 128-event class with the memo: no attribute to raise)
-template <class M, bool MEMO>
+template <class M, bool MEMO, bool EXPLAIN = false>
 hipError_t launch_class(const WTableArgs& p, uint32_t grid, uint32_t pass2, hipStream_t s) {
     constexpr size_t lds = (size_t)(TW<M>::EV + (MEMO ? TW<M>::EV : 0)) * C_LANES * 4;
     static_assert(lds <= 64u * 1024u, "dynamic LDS within the default limit");
-    hipLaunchKernelGGL((wtable_search<M, MEMO>), dim3(grid), dim3(C_LANES), lds, s, p, pass2);
+    hipLaunchKernelGGL((wtable_search<M, MEMO, EXPLAIN>), dim3(grid), dim3(C_LANES), lds, s, p, pass2);
     return hipGetLastError();
 }
 
@@ -295,6 +308,25 @@ hipError_t launch_table(const WTableArgs& p, const uint32_t grid1[3], const uint
         if (e == hipSuccess && (classes & 1u)) e = launch_class<uint32_t, false>(p, g[0], pass2, s);
         if (e == hipSuccess && (classes & 2u)) e = launch_class<uint64_t, false>(p, g[1], pass2, s);
         if (e == hipSuccess && (classes & 4u)) e = launch_class<M128, false>(p, g[2], pass2, s);
+    }
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(wtable_finish, dim3(1), dim3(C_LANES), 0, s, p);
+    return hipGetLastError();
+}
+
+// The explain call's launches (include/qsmd.h qsmd_explain_batch): launch_table
+// with the EXPLAIN instantiations, always the plain search (p.memo null); the
+// caller has run launch_explain_prepare on the stream.
+hipError_t launch_table_explain(const WTableArgs& p, const uint32_t grid1[3], const uint32_t grid2[3], uint32_t classes,
+                                hipStream_t s) {
+    const uint32_t gb = (uint32_t)std::min<uint64_t>(std::max<uint64_t>((p.s.n_hist + 63) / 64, 1), 4096);
+    hipLaunchKernelGGL(wtable_bin, dim3(gb), dim3(C_LANES), 0, s, p);
+    hipError_t e = hipGetLastError();
+    for (uint32_t pass2 = 0; pass2 < (p.budget ? 2u : 1u) && e == hipSuccess; ++pass2) {
+        const uint32_t* g = pass2 ? grid2 : grid1;
+        if (e == hipSuccess && (classes & 1u)) e = launch_class<uint32_t, false, true>(p, g[0], pass2, s);
+        if (e == hipSuccess && (classes & 2u)) e = launch_class<uint64_t, false, true>(p, g[1], pass2, s);
+        if (e == hipSuccess && (classes & 4u)) e = launch_class<M128, false, true>(p, g[2], pass2, s);
     }
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(wtable_finish, dim3(1), dim3(C_LANES), 0, s, p);

@@ -9,5 +9,6 @@ from .codec import Left, Right, encode, decode_history, STATUS_NAMES  # noqa: F4
 from .models import (BANK, TICKET, Bank, TicketDispenser, DeviceModel, TableModel, ModelError,  # noqa: F401
                      EncodeError, WideTableModel, KeyedTableModel)
 from .linearisability import (linearisable, linearisable_batch, trace, wellformed,  # noqa: F401
-                              replay_witness, CheckResult, NotSequential, BudgetExceeded)
+                              replay_witness, CheckResult, NotSequential, BudgetExceeded,
+                              explain, explain_batch, explanation_from_path, Explanation, ExplainResult)
 from . import device, gen  # noqa: F401

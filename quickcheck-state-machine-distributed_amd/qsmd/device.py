@@ -35,6 +35,11 @@ TASK_DTYPE = np.dtype([("hist", "<u4"), ("depth", "<u2"), ("reserved", "<u2"),
 assert TASK_DTYPE.itemsize == 32
 
 
+# qsmd_explain (include/qsmd.h, the explain calls)
+EXPLAIN_DTYPE = np.dtype([("depth", "<u2"), ("reserved", "<u2"), ("reserved2", "<u4"), ("state", "<u8")])
+assert EXPLAIN_DTYPE.itemsize == 16
+
+
 class Frontier(ctypes.Structure):
     _fields_ = [("status", ctypes.c_uint32), ("depth", ctypes.c_uint32),
                 ("top_nodes", ctypes.c_uint64), ("n_tasks", ctypes.c_uint64)]
@@ -74,6 +79,8 @@ EXPORTS = {
     "qsmd_gen_ktable_batch_device": (_I, [_P, _P, _U64, _U64, _U32, _P, _P, _P, _P]),
     "qsmd_check_batch": (_I, [_P, _U32, _P, _U64, _P, _U64, _P, _U32, _U64, _P, _P, _P, _P]),
     "qsmd_check_batch_device": (_I, [_P, _U32, _P, _U64, _P, _U64, _P, _U32, _U64, _P, _P, _P, _P, _P]),
+    "qsmd_explain_batch": (_I, [_P, _U32, _P, _U64, _P, _U64, _P, _U32, _U64, _P, _P, _P, _P, _P]),
+    "qsmd_explain_batch_device": (_I, [_P, _U32, _P, _U64, _P, _U64, _P, _U32, _U64, _P, _P, _P, _P, _P, _P]),
     "qsmd_last_kernel_ms": (_I, [_P, ctypes.POINTER(ctypes.c_float)]),
     "qsmd_timing_reset": (_I, [_P]),
     "qsmd_timing_read": (_I, [_P, _P, _P, _U64, ctypes.POINTER(_U64)]),
@@ -220,6 +227,47 @@ class Context:
             self._h, model_id, hdr_ptr, n_hist, events_ptr, n_events, m0, flags, max_nodes,
             status_ptr, nodes_ptr, witness_ptr, totals_ptr, stream)
         self._check(rc, "qsmd_check_batch_device")
+
+    def explain_arrays(self, model_id, hdr, events, model0=None, flags=QSMD_FLAG_EXHAUSTIVE, max_nodes=0,
+                       path=None):
+        """qsmd_explain_batch on a host-memory batch (the table models): the
+        check call's status and nodes and, per history, the deepest
+        linearised path of its search.  Returns (status u8[n], nodes u64[n],
+        path u8[n_events] in the witness layout, explain EXPLAIN_DTYPE[n],
+        totals dict).  ``path``: the bytes the call starts from (an
+        ENCODE_ERROR slot keeps them); default all 0xFF."""
+        hdr = np.ascontiguousarray(hdr, dtype=codec.HDR_DTYPE)
+        events = np.ascontiguousarray(events, dtype=codec.EV_DTYPE)
+        n = len(hdr)
+        status = np.empty(n, dtype=np.uint8)
+        nodes = np.empty(n, dtype=np.uint64)
+        if path is None:
+            path = np.full(len(events), 0xFF, dtype=np.uint8)
+        else:
+            path = np.array(path, dtype=np.uint8)
+            if path.shape != (len(events),):
+                raise ValueError("one path byte per event")
+        # (never a NULL output: an empty array still has an address)
+        path_buf = path if len(path) else np.empty(1, dtype=np.uint8)
+        explain = np.zeros(max(n, 1), dtype=EXPLAIN_DTYPE)
+        tot = Totals()
+        m0 = ctypes.cast(ctypes.pointer(model0), ctypes.c_void_p) if model0 is not None else None
+        rc = self._lib.qsmd_explain_batch(
+            self._h, model_id, _ptr(hdr) if n else None, n, _ptr(events) if len(events) else None, len(events),
+            m0, flags, max_nodes, _ptr(status) if n else None, _ptr(nodes) if n else None, _ptr(path_buf),
+            _ptr(explain), ctypes.byref(tot))
+        self._check(rc, "qsmd_explain_batch")
+        return status, nodes, path, explain[:n], tot.as_dict()
+
+    def explain_device(self, model_id, hdr_ptr, n_hist, events_ptr, n_events, status_ptr, path_ptr, explain_ptr,
+                       nodes_ptr=None, totals_ptr=None, model0=None, flags=QSMD_FLAG_EXHAUSTIVE, max_nodes=0,
+                       stream=None):
+        """qsmd_explain_batch_device: raw device pointers (ints), async on stream."""
+        m0 = ctypes.cast(ctypes.pointer(model0), ctypes.c_void_p) if model0 is not None else None
+        rc = self._lib.qsmd_explain_batch_device(
+            self._h, model_id, hdr_ptr, n_hist, events_ptr, n_events, m0, flags, max_nodes,
+            status_ptr, nodes_ptr, path_ptr, explain_ptr, totals_ptr, stream)
+        self._check(rc, "qsmd_explain_batch_device")
 
     def last_kernel_ms(self):
         ms = ctypes.c_float()

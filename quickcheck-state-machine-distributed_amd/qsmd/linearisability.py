@@ -13,6 +13,9 @@
   search to fall back to.  Model exceptions propagate as in Haskell
   (:class:`~qsmd.models.ModelError` for ``Map.!``, test/Bank.hs:128).
 * :func:`linearisable_batch` is the throughput entry point.
+* :func:`explain_batch` / :func:`explain` (table models) say where a history
+  went wrong: the deepest linearised path of its search, the model there and
+  the operations that could not follow (:class:`Explanation`).
 * :func:`trace` (src/Linearisability.hs:73-93) and :func:`wellformed`
   (src/Linearisability.hs:97-135) are host utilities; :func:`replay_witness`
   re-checks a GPU witness against the host model.
@@ -29,7 +32,8 @@ from .models import (BY_ID, BY_NAME, DeviceModel, EncodeError, KeyedTableModel, 
                      WideTableModel)
 
 __all__ = ["linearisable", "linearisable_batch", "trace", "wellformed", "replay_witness",
-           "CheckResult", "NotSequential", "BudgetExceeded", "wellformed_batch"]
+           "CheckResult", "NotSequential", "BudgetExceeded", "wellformed_batch",
+           "explain", "explain_batch", "explanation_from_path", "Explanation", "ExplainResult"]
 
 
 class BudgetExceeded(RuntimeError):
@@ -320,3 +324,184 @@ def replay_witness(model, history, witness, model0=None) -> bool:
                for ii, (pp, (kk, _)) in enumerate(history)):
             return False
     return True
+
+
+# ---------------------------------------------------------------------------
+# explain: the deepest linearised path of a search (include/qsmd.h
+# qsmd_explain_batch; the table models)
+# ---------------------------------------------------------------------------
+
+def _first(history, removed, kind, pid=None):
+    """The first remaining event of ``kind`` (of ``pid``), or None."""
+    return next((i for i, (p, (k, _)) in enumerate(history)
+                 if i not in removed and k == kind and (pid is None or p == pid)), None)
+
+
+@dataclass
+class Explanation:
+    """Where the search of one history stood at the end of its reported path.
+
+    ``prefix``: the path's operations ``(pid, inv, resp)``; ``model``: the
+    model value after them; ``stuck``: for every candidate there (the
+    remaining invocations below the first remaining response, in order)
+    ``(pid, inv, resp or None, outcome)``, the outcome one of ``"no response"``
+    (the pid has no remaining response: no child), ``"postcondition false"``,
+    ``"raises"`` and -- never on a NONLINEARISABLE path, whose end is a node
+    no candidate passes; on a BUDGET path (the search stopped early) or a
+    MODEL_ERROR path (an earlier candidate's subtree failed before the raising
+    one was tried) -- ``"passes"``."""
+    status: str
+    prefix: list
+    model: object
+    stuck: list
+    model0: object = None
+    device_model: DeviceModel | None = None
+
+    def pretty(self) -> str:
+        """The prefix in the format of :func:`trace` (the model before each
+        event, the operations in path order), then the model reached and one
+        line per stuck candidate."""
+        m = self.device_model
+        hist = []
+        for pid, inv, resp in self.prefix:
+            hist += [(pid, ("L", inv)), (pid, ("R", resp))]
+        out = [trace(m.transition, self.model0, hist, model=m), f"{m.show_model(self.model)}\n"]
+        for pid, inv, resp, outcome in self.stuck:
+            r = "" if resp is None else f" <== {m.show_resp(resp)}"
+            out.append(f"  =/=> {m.show_inv(inv)}{r}  [{pretty_print_pid(pid)}]: {outcome}\n")
+        return "".join(out)
+
+
+def explanation_from_path(model, history, path, status, model0=None) -> Explanation:
+    """The :class:`Explanation` a reported path stands for (pure host code).
+
+    ``path``: invocation event indices, one per level, replayed by the rule of
+    :func:`replay_witness` -- each step pairs the chosen invocation with the
+    first remaining response of its pid and removes the pid's first remaining
+    invocation and that response; the model is advanced with the model's own
+    ``transition``.  ``status``: a status name or number (it is only carried
+    along).  ValueError for a path that is no path of this history."""
+    m = _as_model(model)
+    history = list(history)
+    start = m.init_model if model0 is None else model0
+    cur = start
+    removed, prefix = set(), []
+    for j in path:
+        j = int(j)
+        if not 0 <= j < len(history) or j in removed or history[j][1][0] != "L":
+            raise ValueError(f"path entry {j}: not a remaining invocation")
+        pid, (_, inv) = history[j]
+        r = _first(history, removed, "R", pid)
+        if r is None:
+            raise ValueError(f"path entry {j}: its pid has no remaining response")
+        resp = history[r][1][1]
+        prefix.append((pid, inv, resp))
+        cur = m.transition(m.transition(cur, ("L", inv)), ("R", resp))
+        removed |= {_first(history, removed, "L", pid), r}
+    first_resp = _first(history, removed, "R")
+    stuck = []
+    for i, (pid, (kind, inv)) in enumerate(history[:len(history) if first_resp is None else first_resp]):
+        if i in removed or kind != "L":
+            continue
+        r = _first(history, removed, "R", pid)
+        if r is None:
+            stuck.append((pid, inv, None, "no response"))
+            continue
+        resp = history[r][1][1]
+        try:
+            outcome = "passes" if m.postcondition(cur, inv, resp) else "postcondition false"
+        except ModelError:
+            outcome = "raises"
+        stuck.append((pid, inv, resp, outcome))
+    name = status if isinstance(status, str) else codec.STATUS_NAMES[int(status)]
+    return Explanation(name, prefix, cur, stuck, start, m)
+
+
+@dataclass
+class ExplainResult(CheckResult):
+    """:class:`CheckResult` of an explain call: ``witness`` holds the reported
+    paths (the witness layout), ``depth`` / ``state`` the qsmd_explain records."""
+    histories: list = field(default_factory=list)
+    depth: np.ndarray | None = None
+    state: np.ndarray | None = None
+    model0: object = None
+
+    def path_of(self, i):
+        """Invocation-event indices of history i's reported path."""
+        h = self.batch.hdr[i]
+        out = []
+        for x in self.witness[h["ev_off"]: h["ev_off"] + h["n_ev"]]:
+            if x == codec.WITNESS_END:
+                break
+            out.append(int(x))
+        return out
+
+    def witness_of(self, i):
+        return self.path_of(i) if self.status[i] == codec.STATUS_LIN else None
+
+    def state_of(self, i):
+        """The device's state record of history i as a model value."""
+        return decode_state(self.batch.model, int(self.state[i]))
+
+    def explanation(self, i) -> Explanation:
+        if self.status[i] == codec.STATUS_ENCODE_ERROR:
+            raise EncodeError(self.batch.encode_errors.get(i, "history cannot be encoded"))
+        e = explanation_from_path(self.batch.model, self.histories[i], self.path_of(i), int(self.status[i]),
+                                  self.model0)
+        if len(e.prefix) != int(self.depth[i]) or tuple_or(e.model) != tuple_or(self.state_of(i)):
+            raise RuntimeError(f"history {i}: the path does not replay to the device's record")
+        return e
+
+
+def tuple_or(x):
+    """A keyed model's value as a plain tuple (its in-between values compare
+    as one, but print their class); any other value as it is."""
+    return tuple(x) if isinstance(x, tuple) else x
+
+
+def decode_state(model, word):
+    """A qsmd_explain ``state`` word as a value of ``model``: the state index
+    (table and wide table models), key k's component state index in bits
+    8k .. 8k + 7 (keyed models)."""
+    m = _as_model(model)
+    if isinstance(m, KeyedTableModel):
+        return tuple(m.component.states[(word >> (8 * k)) & 0xFF] for k in range(m.n_keys))
+    if isinstance(m, TableModel):
+        return m.states[word]
+    raise NotImplementedError("explain: the table models only")
+
+
+def explain_batch(model, histories, model0=None, *, max_nodes=0, ctx=None) -> ExplainResult:
+    """Explain many histories in one device call (qsmd_explain_batch; a
+    :class:`TableModel`, :class:`WideTableModel` or :class:`KeyedTableModel`):
+    status and nodes of :func:`linearisable_batch` without a memo, and per
+    history the deepest linearised path of the search -- always the plain
+    search, for a keyed model on the product; a history whose search passes
+    ``max_nodes`` reads ``budget`` with the deepest path seen so far."""
+    m = _as_model(model)
+    if not isinstance(m, (TableModel, KeyedTableModel)):
+        raise NotImplementedError("explain: the table models only (TableModel, WideTableModel, KeyedTableModel)")
+    histories = [list(h) for h in histories]
+    batch = codec.encode(m, histories, model0)
+    packed = m.pack_model0(model0, m.new_account_map(model0))
+    ctx = ctx or device.default_context()
+    if isinstance(m, WideTableModel):
+        if ctx.wide_table is not m:
+            ctx.set_wide_table(m)
+    elif isinstance(m, TableModel):
+        if ctx.table is not m:
+            ctx.set_table(m)
+    elif ctx.keyed_table is not m:
+        ctx.set_keyed_table(m)
+    status, nodes, path, rec, totals = ctx.explain_arrays(m.model_id, batch.hdr, batch.events, packed,
+                                                          device.QSMD_FLAG_EXHAUSTIVE, max_nodes)
+    return ExplainResult(batch, status, nodes, path, totals, histories, rec["depth"].copy(), rec["state"].copy(),
+                         model0)
+
+
+def explain(transition, postcondition, model0, history, *, max_nodes=0, ctx=None) -> Explanation:
+    """:func:`explain_batch` for one history, with :func:`linearisable`'s
+    signature: the :class:`Explanation` of its search (``.status`` says how it
+    ended; :class:`EncodeError` for a history that cannot be encoded)."""
+    m = _device_model(transition, postcondition)
+    return explain_batch(m, [history], model0, max_nodes=max_nodes, ctx=ctx).explanation(0)

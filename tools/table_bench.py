@@ -46,9 +46,14 @@ checked key by key), crossed with the budgets and memo sizes; a line carries
 shape the --generated batch (default 4, 16 and 0.39: P is the probability that
 a history gets its one response bug, 1 - 0.97^K for 3 % per operation).
 
+--explain: every configuration is also timed as an explain call
+(qsmd_explain_batch_device: the check's search with the deepest linearised path
+of every history recorded, always without a memo and on the product), the two
+interleaved; a line carries "call": "check" or "explain".
+
     python tools/table_bench.py [--budgets default,0] [--memo 0,64,256,1024,4096] [--distinct 65536] [--n 1048576]
                                 [--wide 0|1|both] [--model register|kv] [--generated] [--seed S] [--keyed K]
-                                [--local 0,1] [--clients C] [--ops K] [--p-bug P]
+                                [--local 0,1] [--clients C] [--ops K] [--p-bug P] [--explain]
 """
 
 import argparse
@@ -88,6 +93,7 @@ def main():
     ap.add_argument("--clients", type=int, default=4)
     ap.add_argument("--ops", type=int, default=16)
     ap.add_argument("--p-bug", type=float, default=0.39)
+    ap.add_argument("--explain", action="store_true")
     args = ap.parse_args()
     if args.local != "0" and not args.keyed:
         ap.error("--local is the keyed path's (--keyed K)")
@@ -183,10 +189,14 @@ def main():
     d_st = torch.empty(n, dtype=torch.uint8, device=dev)
     d_nd = torch.empty(n, dtype=torch.int64, device=dev)
     d_tot = torch.zeros(8, dtype=torch.int64, device=dev)
+    if args.explain:
+        d_path = torch.empty(n_events, dtype=torch.uint8, device=dev)
+        d_rec = torch.empty(n * 16, dtype=torch.uint8, device=dev)
     default = ctx.get_param("table_budget")
-    cross = [(b, int(e), mid, int(loc)) for _ in range(args.rounds) for b in args.budgets.split(",")
-             for e in args.memo.split(",") for mid in ids for loc in (args.local.split(",") if mid == 5 else "0")]
-    for b, entries, mid, local in cross:
+    cross = [(b, int(e), mid, int(loc), call) for _ in range(args.rounds) for b in args.budgets.split(",")
+             for e in args.memo.split(",") for mid in ids for loc in (args.local.split(",") if mid == 5 else "0")
+             for call in (("check", "explain") if args.explain else ("check",))]
+    for b, entries, mid, local, call in cross:
         d_hdr, d_ev = d_hdrs[mid], d_evs.get(mid, next(iter(d_evs.values())))
         budget = default if b == "default" else int(b)
         ctx.set_param("table_budget", budget)
@@ -198,8 +208,13 @@ def main():
         for k in range(args.warmup + args.calls):
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             e0.record()
-            ctx.check_device(mid, d_hdr.data_ptr(), n, d_ev.data_ptr(), n_events, d_st.data_ptr(), d_nd.data_ptr(),
-                             None, d_tot.data_ptr(), max_nodes=args.max_nodes, stream=stream)
+            if call == "explain":
+                ctx.explain_device(mid, d_hdr.data_ptr(), n, d_ev.data_ptr(), n_events, d_st.data_ptr(),
+                                   d_path.data_ptr(), d_rec.data_ptr(), d_nd.data_ptr(), d_tot.data_ptr(),
+                                   max_nodes=args.max_nodes, stream=stream)
+            else:
+                ctx.check_device(mid, d_hdr.data_ptr(), n, d_ev.data_ptr(), n_events, d_st.data_ptr(),
+                                 d_nd.data_ptr(), None, d_tot.data_ptr(), max_nodes=args.max_nodes, stream=stream)
             e1.record()
             torch.cuda.synchronize()
             if k >= args.warmup:
@@ -207,7 +222,7 @@ def main():
         tot = d_tot.cpu().numpy()
         med = statistics.median(ms)
         print(json.dumps({
-            "model_id": mid,
+            "model_id": mid, "call": call,
             "workload": what,
             "table_budget": budget, "is_default": budget == default, "table_memo": entries,
             "memo_knob": "ktable_memo" if mid == 5 else "table_memo", "table_memo_hits": ctx.table_memo_hits(), "calls": args.calls,
