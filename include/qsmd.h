@@ -492,6 +492,65 @@ int qsmd_explain_batch_device(qsmd_ctx* ctx, uint32_t model_id,
                               uint8_t* path_dev, qsmd_explain* explain_dev,
                               qsmd_totals* totals_dev, void* stream);
 
+/* ----------------------------------------------------------------- pending
+ * Let pending invocations take effect (QSMD_MODEL_TABLE only; opt-in).
+ *
+ * The check calls follow the reference: an invocation whose pid has no
+ * remaining response (a crashed client, a timeout) is an operation that never
+ * happened.  qsmd_check_pending_batch also lets it take effect, at any point
+ * after its invocation, with a response nobody saw.  The search is the check
+ * call's with two changes:
+ *
+ *   1. A candidate (state s, invocation i) whose pid has no remaining
+ *      response has one child per response symbol r, in ascending order, with
+ *      bit r of post[s][i] set and bit r of post_err[s][i] clear: an *assumed*
+ *      response.  Each is one counted node (max_nodes is tested before it);
+ *      its postcondition is not evaluated again; its state is
+ *      on_resp[on_inv[s][i]][r]; its remaining set loses the pid's first
+ *      remaining invocation and no response.  No allowed symbol: no child, no
+ *      node, as today.
+ *   2. A non-empty history that holds no response event at all and whose root
+ *      has no child is LINEARISABLE with 0 nodes and an empty witness.
+ *
+ * A pending invocation that is never chosen stays in the remaining set; a
+ * node without children succeeds, which reads "it never took effect".  On a
+ * history with nothing pending the call equals qsmd_check_batch in status,
+ * nodes and witness.  With raise tables the call can read MODEL_ERROR where
+ * the check call reads LINEARISABLE: an assumed operation can lead the search
+ * to a raising postcondition (the reference's first-raise rule on more paths).
+ *
+ * With QSMD_FLAG_WITNESS, assumed_out[ev_off + d] is the response symbol
+ * assumed at witness level d, or QSMD_ASSUMED_NONE for an observed response
+ * (written for the levels of the witness and its terminator; the witness
+ * layout, n_events bytes; may be NULL).  A witness can be as long as the
+ * history has invocations.  Replay: an assumed level removes only the pid's
+ * first remaining invocation.
+ *
+ * "table_budget", max_nodes, the time limit, the totals, the probe and the
+ * ENCODE_ERROR rules are the check call's; the knob "table_memo" is ignored.
+ * Models 1, 2, 4, 5 and QSMD_FLAG_EARLY_EXIT_BATCH return
+ * QSMD_ERR_UNSUPPORTED. */
+#define QSMD_ASSUMED_NONE 0xFFu
+
+/* Host memory, synchronous (as qsmd_check_batch). */
+int qsmd_check_pending_batch(qsmd_ctx* ctx, uint32_t model_id,
+                             const qsmd_hdr* hdr, uint64_t n_hist,
+                             const qsmd_event* events, uint64_t n_events,
+                             const void* model0, uint32_t flags, uint64_t max_nodes,
+                             uint8_t* status_out, uint64_t* nodes_out,
+                             uint8_t* witness_out, qsmd_totals* totals_out,
+                             uint8_t* assumed_out);
+
+/* Device memory, asynchronous on `stream` (as qsmd_check_batch_device). */
+int qsmd_check_pending_batch_device(qsmd_ctx* ctx, uint32_t model_id,
+                                    const qsmd_hdr* hdr_dev, uint64_t n_hist,
+                                    const qsmd_event* events_dev, uint64_t n_events,
+                                    const void* model0_host, uint32_t flags,
+                                    uint64_t max_nodes,
+                                    uint8_t* status_dev, uint64_t* nodes_dev,
+                                    uint8_t* witness_dev, qsmd_totals* totals_dev,
+                                    void* stream, uint8_t* assumed_dev);
+
 /* Safety net: a search launch whose lanes run longer than this wall time
  * stops and reports QSMD_STATUS_BUDGET for the unfinished histories (default
  * 120000 ms; 0 disables).  Not part of the reference semantics. */

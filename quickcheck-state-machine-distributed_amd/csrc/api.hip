@@ -870,8 +870,10 @@ static int check_table_locked(qsmd_ctx* c, const qsmd_hdr* hdr, uint64_t n_hist,
                               uint64_t n_events, const void* model0, uint32_t flags, uint64_t max_nodes,
                               uint8_t* status, uint64_t* nodes, uint8_t* witness, qsmd_totals* totals,
                               hipStream_t s, uint32_t route, uint8_t* path = nullptr,
-                              qsmd_explain* explain = nullptr) {
+                              qsmd_explain* explain = nullptr, bool pending = false, uint8_t* assumed = nullptr) {
     constexpr bool WIDE = KIND == kTabWide, KEYED = KIND == kTabKeyed;
+    // pending: a qsmd_check_pending_batch call (model 3 only) -- the same
+    // launches with the search kernels of csrc/tpending.hip, never the memo
     // explain != null: a qsmd_explain_batch call -- the same launches with the
     // EXPLAIN instantiations, always the plain search on the product (no
     // memo, no local mode, no witness: the path is the witness)
@@ -1020,7 +1022,7 @@ static int check_table_locked(qsmd_ctx* c, const qsmd_hdr* hdr, uint64_t n_hist,
     // ("ktable_memo"; "table_memo" does not reach it, nor "ktable_memo" the
     // other two), 48-byte entries and full-word epochs; its sizing is
     // ktable_memo_plan (ktable_host.h).
-    const uint64_t memo_entries = explain ? 0 : (KEYED ? c->ktable_memo : c->table_memo);
+    const uint64_t memo_entries = explain || pending ? 0 : (KEYED ? c->ktable_memo : c->table_memo);
     if (memo_entries && c->table_budget) {
         uint64_t gm;
         size_t need;
@@ -1068,7 +1070,11 @@ static int check_table_locked(qsmd_ctx* c, const qsmd_hdr* hdr, uint64_t n_hist,
         for (int k = 0; k < 3; ++k) grid2[k] = (uint32_t)gm;
     }
     const uint32_t classes = (route & kClassesKnown) ? (route & 7u) : 7u;
-    if (explain) {
+    if (pending) {
+        if constexpr (KIND == kTabNarrow)
+            HIP_TRY(c, launch_table_pending(p, grid1, grid2, classes, p.s.witness ? assumed : nullptr, s),
+                    "table pending launch");
+    } else if (explain) {
         HIP_TRY(c, launch_explain_prepare(p.s, (uint64_t)state0, path, p.explain, s), "explain prepare launch");
         HIP_TRY(c, launch_table_explain(p, grid1, grid2, classes, s), "table explain launch");
     } else {
@@ -1675,6 +1681,90 @@ int qsmd_explain_batch(qsmd_ctx* c, uint32_t model_id, const qsmd_hdr* hdr, uint
     if (n_hist && nodes_out) std::memcpy(nodes_out, c->pin + o_nd, n_hist * 8);
     if (n_events) std::memcpy(path_out, c->pin + o_p, n_events);
     if (n_hist) std::memcpy(explain_out, c->pin + o_x, n_hist * sizeof(qsmd_explain));
+    if (totals_out) std::memcpy(totals_out, c->pin + o_tot, sizeof(qsmd_totals));
+    return QSMD_OK;
+}
+
+// qsmd_check_pending_batch's route: QSMD_MODEL_TABLE only, through
+// check_table_locked with the search kernels of csrc/tpending.hip.
+static int pending_device_locked(qsmd_ctx* c, uint32_t model_id, const qsmd_hdr* hdr, uint64_t n_hist,
+                                 const qsmd_event* events, uint64_t n_events, const void* model0, uint32_t flags,
+                                 uint64_t max_nodes, uint8_t* status, uint64_t* nodes, uint8_t* witness,
+                                 uint8_t* assumed, qsmd_totals* totals, hipStream_t s, uint32_t route) {
+    if (model_id == QSMD_MODEL_BANK || model_id == QSMD_MODEL_TICKET || model_id == QSMD_MODEL_WTABLE ||
+        model_id == QSMD_MODEL_KTABLE)
+        return fail(c, QSMD_ERR_UNSUPPORTED, "qsmd_check_pending_batch: QSMD_MODEL_TABLE only (3)");
+    if (model_id != QSMD_MODEL_TABLE) return fail(c, QSMD_ERR_ARG, "unknown model_id");
+    return check_table_locked<kTabNarrow>(c, hdr, n_hist, events, n_events, model0, flags, max_nodes, status, nodes,
+                                          witness, totals, s, route, nullptr, nullptr, true, assumed);
+}
+
+int qsmd_check_pending_batch_device(qsmd_ctx* c, uint32_t model_id, const qsmd_hdr* hdr_dev, uint64_t n_hist,
+                                    const qsmd_event* events_dev, uint64_t n_events, const void* model0_host,
+                                    uint32_t flags, uint64_t max_nodes, uint8_t* status_dev, uint64_t* nodes_dev,
+                                    uint8_t* witness_dev, qsmd_totals* totals_dev, void* stream,
+                                    uint8_t* assumed_dev) {
+    if (!c) return QSMD_ERR_ARG;
+    std::lock_guard<std::mutex> g(c->mu);
+    hipStream_t s = stream ? static_cast<hipStream_t>(stream) : ctx_stream(c);
+    if (!s) return fail(c, QSMD_ERR_DEVICE, "hipStreamCreate");
+    return pending_device_locked(c, model_id, hdr_dev, n_hist, events_dev, n_events, model0_host, flags, max_nodes,
+                                 status_dev, nodes_dev, witness_dev, assumed_dev, totals_dev, s, 0u);
+}
+
+int qsmd_check_pending_batch(qsmd_ctx* c, uint32_t model_id, const qsmd_hdr* hdr, uint64_t n_hist,
+                             const qsmd_event* events, uint64_t n_events, const void* model0, uint32_t flags,
+                             uint64_t max_nodes, uint8_t* status_out, uint64_t* nodes_out, uint8_t* witness_out,
+                             qsmd_totals* totals_out, uint8_t* assumed_out) {
+    if (!c) return QSMD_ERR_ARG;
+    if (n_hist && (!hdr || !status_out)) return fail(c, QSMD_ERR_ARG, "null hdr/status");
+    if (n_events && !events) return fail(c, QSMD_ERR_ARG, "null events");
+    std::lock_guard<std::mutex> g(c->mu);
+    HIP_TRY(c, hipSetDevice(c->device), "hipSetDevice");
+    hipStream_t s = ctx_stream(c);
+    if (!s) return fail(c, QSMD_ERR_DEVICE, "hipStreamCreate");
+    HIP_TRY(c, order_after_previous(c, s), "order after the previous call");
+    const bool want_w = (flags & QSMD_FLAG_WITNESS) && witness_out;
+    const bool want_a = want_w && assumed_out;
+    // io layout: [hdr | events | witness | assumed] copied in (both 0xFF),
+    // [witness | assumed | status | nodes | totals] copied out
+    const size_t o_hdr = 0;
+    const size_t o_ev = o_hdr + align_up(n_hist * sizeof(qsmd_hdr), 16);
+    const size_t o_w = o_ev + align_up(n_events * sizeof(qsmd_event), 16);
+    const size_t o_a = o_w + align_up(want_w ? n_events : 0, 16);
+    const size_t o_st = o_a + align_up(want_a ? n_events : 0, 16);
+    const size_t o_nd = o_st + align_up(n_hist, 16);
+    const size_t o_tot = o_nd + align_up(n_hist * 8, 16);
+    const size_t need = o_tot + align_up(sizeof(qsmd_totals), 16);
+    int rc = grow(c, &c->io, &c->io_bytes, need);
+    if (rc) return rc;
+    rc = grow_pinned(c, need);
+    if (rc) return rc;
+    if (n_hist) std::memcpy(c->pin + o_hdr, hdr, n_hist * sizeof(qsmd_hdr));
+    if (n_events) std::memcpy(c->pin + o_ev, events, n_events * sizeof(qsmd_event));
+    if (want_w) std::memset(c->pin + o_w, 0xFF, n_events);
+    if (want_a) std::memset(c->pin + o_a, 0xFF, n_events);
+    if (o_st) HIP_TRY(c, hipMemcpyAsync(c->io, c->pin, o_st, hipMemcpyHostToDevice, s), "H2D inputs");
+    uint32_t route = kClassesKnown;         // the width classes present (one launch per non-empty class)
+    for (uint64_t i = 0; i < n_hist && (route & 7u) != 7u; ++i)
+        route |= hdr[i].n_ev <= 32u ? 1u : (hdr[i].n_ev <= 64u ? 2u : 4u);
+    rc = pending_device_locked(c, model_id, reinterpret_cast<qsmd_hdr*>(c->io + o_hdr), n_hist,
+                               reinterpret_cast<qsmd_event*>(c->io + o_ev), n_events, model0, flags, max_nodes,
+                               reinterpret_cast<uint8_t*>(c->io + o_st), reinterpret_cast<uint64_t*>(c->io + o_nd),
+                               want_w ? reinterpret_cast<uint8_t*>(c->io + o_w) : nullptr,
+                               want_a ? reinterpret_cast<uint8_t*>(c->io + o_a) : nullptr,
+                               reinterpret_cast<qsmd_totals*>(c->io + o_tot), s, route);
+    if (rc) {
+        (void)hipStreamSynchronize(s);      // (the copy in may still read the pinned buffer)
+        return rc;
+    }
+    HIP_TRY(c, hipMemcpyAsync(c->pin + o_w, c->io + o_w, need - o_w, hipMemcpyDeviceToHost, s), "D2H outputs");
+    HIP_TRY(c, hipStreamSynchronize(s), "hipStreamSynchronize");
+    c->in_flight = false;
+    if (n_hist) std::memcpy(status_out, c->pin + o_st, n_hist);
+    if (n_hist && nodes_out) std::memcpy(nodes_out, c->pin + o_nd, n_hist * 8);
+    if (want_w) std::memcpy(witness_out, c->pin + o_w, n_events);
+    if (want_a) std::memcpy(assumed_out, c->pin + o_a, n_events);
     if (totals_out) std::memcpy(totals_out, c->pin + o_tot, sizeof(qsmd_totals));
     return QSMD_OK;
 }

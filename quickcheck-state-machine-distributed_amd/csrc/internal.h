@@ -429,8 +429,18 @@ struct TableArgs {
 hipError_t launch_table(const TableArgs& p, const uint32_t grid1[3], const uint32_t grid2[3], uint32_t classes,
                         hipStream_t s);
 // the LDS bytes of one workgroup of class k (0, 1, 2)
-// (memo: pass 2 with the state memo, + 8 B per level and lane)
-size_t table_lds_bytes(const TableDev& t, int k, bool memo = false);
+// (memo: pass 2 with the state memo, + 8 B per level and lane; pending: the
+// search of csrc/tpending.hip, a 32-bit stack level per event)
+size_t table_lds_bytes(const TableDev& t, int k, bool memo = false, bool pending = false);
+
+// qsmd_check_pending_batch (csrc/tpending.hip): launch_table's launches with
+// the search kernels that let a pending invocation take effect; assumed: the
+// call's assumed bytes (device, the witness layout) or null.  The binning and
+// the totals kernels are launch_table's own.
+hipError_t launch_table_bin(const TableArgs& p, hipStream_t s);
+hipError_t launch_table_finish(const TableArgs& p, hipStream_t s);
+hipError_t launch_table_pending(const TableArgs& p, const uint32_t grid1[3], const uint32_t grid2[3],
+                                uint32_t classes, uint8_t* assumed, hipStream_t s);
 
 // The explain calls (qsmd_explain_batch): launch_table with the EXPLAIN
 // instantiations of the search kernels, which also write p.path and

@@ -356,9 +356,23 @@ hipError_t launch_class(const TableArgs& p, uint32_t grid, uint32_t pass2, hipSt
 
 }  // namespace
 
-size_t table_lds_bytes(const TableDev& t, int k, bool memo) {
+size_t table_lds_bytes(const TableDev& t, int k, bool memo, bool pending) {
     const size_t ev = k == 0 ? 32 : (k == 1 ? 64 : 128);
-    return ((ev / 2 + ev / 4 + (memo ? ev : 0)) * C_LANES + (size_t)t.blob_words) * 4;
+    // (pending: csrc/tpending.hip's stack, one 32-bit level per event)
+    const size_t stack = pending ? ev : ev / 4;
+    return ((ev / 2 + stack + (memo ? ev : 0)) * C_LANES + (size_t)t.blob_words) * 4;
+}
+
+// The first and the last launch of a table call on their own (csrc/tpending.hip).
+hipError_t launch_table_bin(const TableArgs& p, hipStream_t s) {
+    const uint32_t gb = (uint32_t)std::min<uint64_t>(std::max<uint64_t>((p.s.n_hist + 63) / 64, 1), 4096);
+    hipLaunchKernelGGL(table_bin, dim3(gb), dim3(C_LANES), 0, s, p);
+    return hipGetLastError();
+}
+
+hipError_t launch_table_finish(const TableArgs& p, hipStream_t s) {
+    hipLaunchKernelGGL(table_finish, dim3(1), dim3(C_LANES), 0, s, p);
+    return hipGetLastError();
 }
 
 hipError_t launch_explain_prepare(const SearchArgs& a, uint64_t state0, uint8_t* path, uint4* explain,

@@ -79,9 +79,21 @@ class CheckResult:
     nodes: np.ndarray
     witness: np.ndarray | None
     totals: dict = field(default_factory=dict)
+    # pending="complete" with a witness: per witness level the assumed response
+    # symbol, device.QSMD_ASSUMED_NONE for an observed one (the witness layout)
+    assumed: np.ndarray | None = field(default=None, kw_only=True)
 
     def verdict(self, i):
         return codec.STATUS_NAMES[int(self.status[i])]
+
+    def assumed_of(self, i):
+        """Per level of history i's witness the assumed response symbol (an
+        index into the model's ``resps``), None for an observed response."""
+        w = self.witness_of(i)
+        if w is None or self.assumed is None:
+            return None
+        off = int(self.batch.hdr[i]["ev_off"])
+        return [None if x == device.QSMD_ASSUMED_NONE else int(x) for x in self.assumed[off: off + len(w)]]
 
     def witness_of(self, i):
         """Invocation-event indices of the linearisation of history i."""
@@ -99,7 +111,7 @@ class CheckResult:
 
 def linearisable_batch(model, histories, model0=None, *, max_nodes=0, witness=False,
                        flags=device.QSMD_FLAG_EXHAUSTIVE, ctx=None, table_memo=None,
-                       ktable_local=None) -> CheckResult:
+                       ktable_local=None, pending=None) -> CheckResult:
     """Check many histories in one device call.  ``table_memo`` (table models:
     entries per lane slot of the second pass's state memo, 0 = off) sets the
     context's "table_memo" knob for this call and restores it afterwards;
@@ -107,8 +119,20 @@ def linearisable_batch(model, histories, model0=None, *, max_nodes=0, witness=Fa
     "ktable_memo".  ``ktable_local`` (a :class:`KeyedTableModel` only): None
     leaves the context's "ktable_local" knob alone, True / False set it for
     this call in the same way -- every splittable history is then checked key
-    by key (include/qsmd.h; :meth:`KeyedTableModel.split_history`)."""
+    by key (include/qsmd.h; :meth:`KeyedTableModel.split_history`).
+
+    ``pending`` (a :class:`TableModel` only): None is the reference's rule --
+    an invocation that never got its response is an operation that never
+    happened.  ``"complete"`` also lets it take effect, at any point after its
+    invocation, with any response the model allows (qsmd_check_pending_batch,
+    include/qsmd.h): with ``witness`` the result's ``assumed`` names the
+    responses that were assumed.  With raise tables this can read ``error``
+    where None reads ``lin``; "table_memo" is ignored."""
     m = _as_model(model)
+    if pending not in (None, "complete"):
+        raise ValueError('pending: None or "complete"')
+    if pending and (not isinstance(m, TableModel) or isinstance(m, WideTableModel)):
+        raise NotImplementedError('pending="complete": a TableModel only (QSMD_MODEL_TABLE)')
     batch = codec.encode(m, histories, model0)
     accounts0 = m.new_account_map(model0)
     packed = m.pack_model0(model0, accounts0)
@@ -130,24 +154,29 @@ def linearisable_batch(model, histories, model0=None, *, max_nodes=0, witness=Fa
     if ktable_local is not None and isinstance(m, KeyedTableModel):
         saved_local = ctx.get_param("ktable_local")
         ctx.set_param("ktable_local", 1 if ktable_local else 0)
+    assumed = None
     try:
-        status, nodes, wit, totals = ctx.check_arrays(m.model_id, batch.hdr, batch.events, packed,
-                                                      flags, max_nodes, witness)
+        if pending:
+            status, nodes, wit, assumed, totals = ctx.check_pending_arrays(m.model_id, batch.hdr, batch.events,
+                                                                           packed, flags, max_nodes, witness)
+        else:
+            status, nodes, wit, totals = ctx.check_arrays(m.model_id, batch.hdr, batch.events, packed,
+                                                          flags, max_nodes, witness)
     finally:
         if saved is not None:
             ctx.set_param(knob, saved)
         if saved_local is not None:
             ctx.set_param("ktable_local", saved_local)
-    return CheckResult(batch, status, nodes, wit, totals)
+    return CheckResult(batch, status, nodes, wit, totals, assumed=assumed)
 
 
 def linearisable(transition, postcondition, model0, history, *, max_nodes=0, ctx=None, table_memo=None,
-                 ktable_local=None) -> bool:
+                 ktable_local=None, pending=None) -> bool:
     """``linearisable`` (src/Linearisability.hs:52-69) on the GPU
-    (``table_memo``, ``ktable_local``: see :func:`linearisable_batch`)."""
+    (``table_memo``, ``ktable_local``, ``pending``: see :func:`linearisable_batch`)."""
     m = _device_model(transition, postcondition)
     res = linearisable_batch(m, [history], model0, max_nodes=max_nodes, ctx=ctx, table_memo=table_memo,
-                             ktable_local=ktable_local)
+                             ktable_local=ktable_local, pending=pending)
     st = int(res.status[0])
     if st == codec.STATUS_LIN:
         return True
@@ -281,13 +310,70 @@ def wellformed(pids, history):
 # witness replay (host re-check of a GPU linearisation)
 # ---------------------------------------------------------------------------
 
-def replay_witness(model, history, witness, model0=None) -> bool:
+def _replay_pending(m, history, witness, model0, assumed) -> bool:
+    """:func:`replay_witness` under ``pending="complete"`` (a TableModel):
+    ``assumed[d]`` is None for an observed level, else the index of the
+    response symbol assumed there."""
+    if len(assumed) != len(witness):
+        return False
+    cur = m.init_model if model0 is None else model0
+    removed = set()
+
+    def allowed(state, inv):
+        s, i = m._state(state), m.encode_inv(inv, None)[0]
+        err = 0 if m.post_err is None else int(m.post_err[s, i])
+        return int(m.post[s, i]) & ~err & ((1 << len(m.resps)) - 1)
+
+    for j, a in zip(witness, assumed):
+        if not 0 <= j < len(history) or j in removed or history[j][1][0] != "L":
+            return False
+        pid, (_, inv) = history[j]
+        first_resp = _first(history, removed, "R")
+        if first_resp is not None and j > first_resp:
+            return False
+        r = _first(history, removed, "R", pid)
+        if a is None:
+            if r is None:
+                return False
+            resp = history[r][1][1]
+            if not m.postcondition(cur, inv, resp):
+                return False
+            removed.add(r)
+        else:
+            # assumed: the pid has no remaining response there, the model allows the symbol
+            if r is not None or not 0 <= a < len(m.resps) or not (allowed(cur, inv) >> a) & 1:
+                return False
+            resp = m.resps[a]
+        cur = m.transition(m.transition(cur, ("L", inv)), ("R", resp))
+        removed.add(_first(history, removed, "L", pid))
+    if not witness and any(k == "R" for _, (k, _) in history):
+        return False                    # the root without a child succeeds only with no response at all
+    # a leaf: no candidate has a child, observed or assumed
+    first_resp = _first(history, removed, "R")
+    for i, (p, (k, inv)) in enumerate(history[:len(history) if first_resp is None else first_resp]):
+        if i in removed or k != "L":
+            continue
+        if _first(history, removed, "R", p) is not None or allowed(cur, inv):
+            return False
+    return True
+
+
+def replay_witness(model, history, witness, model0=None, assumed=None) -> bool:
     """Re-run the operations named by ``witness`` (invocation event indices,
     one per level) with the host model: each step pairs the chosen
     invocation with the first remaining response of its pid and removes the
     first remaining invocation and response of that pid (Lemma L1).  True iff
-    every postcondition holds and the final state has no further child."""
+    every postcondition holds and the final state has no further child.
+
+    ``assumed`` (``pending="complete"``, a :class:`TableModel`): one entry
+    per level, None for an observed response or the index of the response
+    symbol assumed there (:meth:`CheckResult.assumed_of`).  An assumed level is
+    replayed with the named response: its pid must have no remaining response
+    there, the model must allow the symbol, and only the invocation is
+    removed."""
     m = _as_model(model)
+    if assumed is not None:
+        return _replay_pending(m, list(history), [int(j) for j in witness], model0, list(assumed))
     if not witness:                     # only `linearisable _ _ _ [] = True` (:59)
         return len(history) == 0
     cur = m.init_model if model0 is None else model0

@@ -51,9 +51,17 @@ a history gets its one response bug, 1 - 0.97^K for 3 % per operation).
 of every history recorded, always without a memo and on the product), the two
 interleaved; a line carries "call": "check" or "explain".
 
+--pending: every configuration is also timed as qsmd_check_pending_batch_device
+(csrc/tpending.hip: pending invocations may take effect) on the same, complete
+batch -- what the wider stack and the extra branch cost where nothing is
+pending -- and on the same histories with clients crashed (tests/pending_ref.py
+crash, probability 0.3 per client), the three interleaved; a line carries
+"call": "check" or "pending" and "batch": "complete" or "crash 0.3".  The
+register batch of the default run only.
+
     python tools/table_bench.py [--budgets default,0] [--memo 0,64,256,1024,4096] [--distinct 65536] [--n 1048576]
                                 [--wide 0|1|both] [--model register|kv] [--generated] [--seed S] [--keyed K]
-                                [--local 0,1] [--clients C] [--ops K] [--p-bug P] [--explain]
+                                [--local 0,1] [--clients C] [--ops K] [--p-bug P] [--explain] [--pending]
 """
 
 import argparse
@@ -94,7 +102,10 @@ def main():
     ap.add_argument("--ops", type=int, default=16)
     ap.add_argument("--p-bug", type=float, default=0.39)
     ap.add_argument("--explain", action="store_true")
+    ap.add_argument("--pending", action="store_true")
     args = ap.parse_args()
+    if args.pending and (args.generated or args.keyed or args.wide != "0" or args.model != "register" or args.explain):
+        ap.error("--pending runs the register batch of the default run alone")
     if args.local != "0" and not args.keyed:
         ap.error("--local is the keyed path's (--keyed K)")
     if (args.clients, args.ops, args.p_bug) != (4, 16, 0.39) and not args.generated:
@@ -185,6 +196,18 @@ def main():
             if args.keyed or not d_evs:     # (without --keyed the events are the same for every id: one copy)
                 d_evs[mid] = torch.from_numpy(np.tile(batch.events, reps).view(np.uint8)).to(dev)
         n_events = per * reps
+        if args.pending:                    # the same histories with clients crashed, tiled alike
+            import pending_ref
+            crash_rng = random.Random("table_bench/crash")
+            batch = codec.encode(m, [pending_ref.crash(h, crash_rng, 0.3) for h in hists])
+            assert not batch.encode_errors
+            per_c = len(batch.events)
+            hdr = np.tile(batch.hdr, reps)
+            hdr["ev_off"] = (hdr["ev_off"].astype(np.int64) + np.repeat(np.arange(reps, dtype=np.int64) * per_c,
+                                                                         args.distinct)).astype(np.uint32)
+            d_hdr_c = torch.from_numpy(hdr.view(np.uint8).copy()).to(dev)
+            d_ev_c = torch.from_numpy(np.tile(batch.events, reps).view(np.uint8)).to(dev)
+            n_events_c = per_c * reps
         what = f"{model['name']} 4x16 p_bug 0.03, {args.distinct} distinct tiled to {n}, device-resident"
     d_st = torch.empty(n, dtype=torch.uint8, device=dev)
     d_nd = torch.empty(n, dtype=torch.int64, device=dev)
@@ -195,7 +218,8 @@ def main():
     default = ctx.get_param("table_budget")
     cross = [(b, int(e), mid, int(loc), call) for _ in range(args.rounds) for b in args.budgets.split(",")
              for e in args.memo.split(",") for mid in ids for loc in (args.local.split(",") if mid == 5 else "0")
-             for call in (("check", "explain") if args.explain else ("check",))]
+             for call in (("check", "explain") if args.explain else
+                          ("check", "pending", "pending/crash") if args.pending else ("check",))]
     for b, entries, mid, local, call in cross:
         d_hdr, d_ev = d_hdrs[mid], d_evs.get(mid, next(iter(d_evs.values())))
         budget = default if b == "default" else int(b)
@@ -212,6 +236,14 @@ def main():
                 ctx.explain_device(mid, d_hdr.data_ptr(), n, d_ev.data_ptr(), n_events, d_st.data_ptr(),
                                    d_path.data_ptr(), d_rec.data_ptr(), d_nd.data_ptr(), d_tot.data_ptr(),
                                    max_nodes=args.max_nodes, stream=stream)
+            elif call == "pending":
+                ctx.check_pending_device(mid, d_hdr.data_ptr(), n, d_ev.data_ptr(), n_events, d_st.data_ptr(),
+                                         d_nd.data_ptr(), None, d_tot.data_ptr(), max_nodes=args.max_nodes,
+                                         stream=stream)
+            elif call == "pending/crash":
+                ctx.check_pending_device(mid, d_hdr_c.data_ptr(), n, d_ev_c.data_ptr(), n_events_c, d_st.data_ptr(),
+                                         d_nd.data_ptr(), None, d_tot.data_ptr(), max_nodes=args.max_nodes,
+                                         stream=stream)
             else:
                 ctx.check_device(mid, d_hdr.data_ptr(), n, d_ev.data_ptr(), n_events, d_st.data_ptr(),
                                  d_nd.data_ptr(), None, d_tot.data_ptr(), max_nodes=args.max_nodes, stream=stream)
@@ -222,7 +254,8 @@ def main():
         tot = d_tot.cpu().numpy()
         med = statistics.median(ms)
         print(json.dumps({
-            "model_id": mid, "call": call,
+            "model_id": mid, "call": call.split("/")[0],
+            **({"batch": "crash 0.3" if call == "pending/crash" else "complete"} if args.pending else {}),
             "workload": what,
             "table_budget": budget, "is_default": budget == default, "table_memo": entries,
             "memo_knob": "ktable_memo" if mid == 5 else "table_memo", "table_memo_hits": ctx.table_memo_hits(), "calls": args.calls,
