@@ -528,6 +528,19 @@ int qsmd_explain_batch_device(qsmd_ctx* ctx, uint32_t model_id,
  *
  * "table_budget", max_nodes, the time limit, the totals, the probe and the
  * ENCODE_ERROR rules are the check call's; the knob "table_memo" is ignored.
+ * Knob "pending_memo" (default 0 = off: exactly the launches above; else a
+ * power of two in 2..2^20, anything else QSMD_ERR_ARG and the old value
+ * stays): the second pass of these two calls, and of no other, keeps
+ * "table_memo"'s exact-count state memo of that many entries per lane slot.
+ * Status, node count, witness, assumed bytes and totals are unchanged; a
+ * max_nodes inside a folded subtree gives BUDGET with nodes == max_nodes, a
+ * count beyond 2^64 - 1 BUDGET with nodes == 2^64 - 1.  The tables are
+ * "table_memo"'s allocation and sizing ("table_memo_grid" included).  A width
+ * class whose memo kernel would pass the device's LDS limit (the 128-event
+ * class with tables over 48 KB) runs the plain second pass.  With
+ * "table_budget" 0 the knob is inert.  qsmd_get_param "pending_memo_hits_last":
+ * the memo's hits in the most recent pending call (waits for it; 0 when that
+ * call ran without the memo); "table_memo_hits_last" is not moved by it.
  * Models 1, 2, 4, 5 and QSMD_FLAG_EARLY_EXIT_BATCH return
  * QSMD_ERR_UNSUPPORTED. */
 #define QSMD_ASSUMED_NONE 0xFFu

@@ -185,6 +185,13 @@ struct qsmd_ctx {
     char* tm = nullptr;
     size_t tm_bytes = 0;
     uint32_t tm_epoch = 0;
+    // qsmd_check_pending_batch's own ("pending_memo", entries per lane slot;
+    // 0 = off): the narrow path's tables, sizing and epochs.  lds_limit: the
+    // LDS bytes a workgroup may hold (a class whose memo kernel needs more
+    // runs the plain pending kernel in pass 2)
+    uint64_t pending_memo = 0;
+    bool pending_memo_call = false;    // the most recent pending call ran the memo
+    size_t lds_limit = 64u * 1024u;
     // QSMD_MODEL_WTABLE (csrc/wtable.hip): the wide table set by
     // qsmd_wtable_set, beside the narrow one.  Its calls use the narrow
     // path's workspace, knobs and memo tables; the paths lay a memo entry out
@@ -404,7 +411,13 @@ int qsmd_open(qsmd_ctx** out, int device) {
         if (hipEventCreate(&e) != hipSuccess) { qsmd_close(c); return QSMD_ERR_DEVICE; }
     }
     hipDeviceProp_t prop;
-    if (hipGetDeviceProperties(&prop, device) == hipSuccess) c->n_cu = prop.multiProcessorCount;
+    if (hipGetDeviceProperties(&prop, device) == hipSuccess) {
+        c->n_cu = prop.multiProcessorCount;
+        // (at least the 64 KB every launch may ask for; the larger of the two
+        // figures: a launch beyond the true limit fails, it does not misbehave)
+        c->lds_limit = std::max<size_t>(
+            c->lds_limit, std::max<size_t>(prop.sharedMemPerBlock, prop.maxSharedMemoryPerMultiProcessor));
+    }
     if (hipEventCreateWithFlags(&c->done_ev, hipEventDisableTiming) != hipSuccess ||
         hipHostMalloc(reinterpret_cast<void**>(&c->probe_host), kProbeWords * 4,
                       hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess) {
@@ -549,6 +562,10 @@ int qsmd_set_param(qsmd_ctx* c, const char* name, uint64_t value) {
         if (value && (value < 2 || value > (1ull << 20) || (value & (value - 1))))
             return fail(c, QSMD_ERR_ARG, "table_memo: 0 (off) or a power of two in 2..2^20");
         c->table_memo = value;
+    } else if (n == "pending_memo") {       // the same for qsmd_check_pending_batch, and for it only
+        if (value && (value < 2 || value > (1ull << 20) || (value & (value - 1))))
+            return fail(c, QSMD_ERR_ARG, "pending_memo: 0 (off) or a power of two in 2..2^20");
+        c->pending_memo = value;
     } else if (n == "ktable_memo") {        // the keyed path's own: QSMD_MODEL_KTABLE calls only
         if (!ktable_memo_ok(value))
             return fail(c, QSMD_ERR_ARG, "ktable_memo: 0 (off) or a power of two in 2..2^20");
@@ -873,7 +890,8 @@ static int check_table_locked(qsmd_ctx* c, const qsmd_hdr* hdr, uint64_t n_hist,
                               qsmd_explain* explain = nullptr, bool pending = false, uint8_t* assumed = nullptr) {
     constexpr bool WIDE = KIND == kTabWide, KEYED = KIND == kTabKeyed;
     // pending: a qsmd_check_pending_batch call (model 3 only) -- the same
-    // launches with the search kernels of csrc/tpending.hip, never the memo
+    // launches with the search kernels of csrc/tpending.hip, the memo under
+    // its own knob ("pending_memo"; "table_memo" does not reach it)
     // explain != null: a qsmd_explain_batch call -- the same launches with the
     // EXPLAIN instantiations, always the plain search on the product (no
     // memo, no local mode, no witness: the path is the witness)
@@ -1021,8 +1039,11 @@ static int check_table_locked(qsmd_ctx* c, const qsmd_hdr* hdr, uint64_t n_hist,
     // 24-bit epochs wrap, not per call.  The keyed path has its own knob
     // ("ktable_memo"; "table_memo" does not reach it, nor "ktable_memo" the
     // other two), 48-byte entries and full-word epochs; its sizing is
-    // ktable_memo_plan (ktable_host.h).
-    const uint64_t memo_entries = explain || pending ? 0 : (KEYED ? c->ktable_memo : c->table_memo);
+    // ktable_memo_plan (ktable_host.h).  A pending call ("pending_memo") uses
+    // the narrow path's tables, sizing and epochs.
+    const uint64_t memo_entries =
+        explain ? 0 : (pending ? c->pending_memo : (KEYED ? c->ktable_memo : c->table_memo));
+    if (pending) c->pending_memo_call = memo_entries && c->table_budget;
     if (memo_entries && c->table_budget) {
         uint64_t gm;
         size_t need;
@@ -1072,7 +1093,8 @@ static int check_table_locked(qsmd_ctx* c, const qsmd_hdr* hdr, uint64_t n_hist,
     const uint32_t classes = (route & kClassesKnown) ? (route & 7u) : 7u;
     if (pending) {
         if constexpr (KIND == kTabNarrow)
-            HIP_TRY(c, launch_table_pending(p, grid1, grid2, classes, p.s.witness ? assumed : nullptr, s),
+            HIP_TRY(c,
+                    launch_table_pending(p, grid1, grid2, classes, p.s.witness ? assumed : nullptr, c->lds_limit, s),
                     "table pending launch");
     } else if (explain) {
         HIP_TRY(c, launch_explain_prepare(p.s, (uint64_t)state0, path, p.explain, s), "explain prepare launch");
@@ -2074,6 +2096,13 @@ int qsmd_get_param(qsmd_ctx* c, const char* name, uint64_t* out) {
         *out = c->probe_host[kProbeTabPass2];
     } else if (n == "table_memo") {
         *out = c->table_memo;
+    } else if (n == "pending_memo") {
+        *out = c->pending_memo;
+    } else if (n == "pending_memo_hits_last") {   // memo hits of the most recent qsmd_check_pending_batch call
+        quiesce(c);
+        *out = c->pending_memo_call
+                   ? c->probe_host[kProbePendHits] | ((uint64_t)c->probe_host[kProbePendHits + 1] << 32)
+                   : 0u;
     } else if (n == "ktable_memo") {
         *out = c->ktable_memo;
     } else if (n == "ktable_local") {

@@ -396,6 +396,7 @@ enum TCnt : uint32_t {
     TC_HEAVY = 3,       // histories over the pass-1 budget, per class: 3 counters
     TC_TIMED = 6,       // the time limit fired
     TC_HITS = 8,        // pass 2's memo hits: one u64 (two counters, 8-byte aligned)
+    TC_PHITS = 10,      // the pending call's ("pending_memo", csrc/tpending.hip): one u64
     TC_N = 16
 };
 constexpr size_t kTabOffBuckets = 256;
@@ -430,17 +431,22 @@ hipError_t launch_table(const TableArgs& p, const uint32_t grid1[3], const uint3
                         hipStream_t s);
 // the LDS bytes of one workgroup of class k (0, 1, 2)
 // (memo: pass 2 with the state memo, + 8 B per level and lane; pending: the
-// search of csrc/tpending.hip, a 32-bit stack level per event)
+// search of csrc/tpending.hip, a 32-bit stack level per event -- and with the
+// memo a count per event, twice the check call's column)
 size_t table_lds_bytes(const TableDev& t, int k, bool memo = false, bool pending = false);
 
 // qsmd_check_pending_batch (csrc/tpending.hip): launch_table's launches with
 // the search kernels that let a pending invocation take effect; assumed: the
 // call's assumed bytes (device, the witness layout) or null.  The binning and
-// the totals kernels are launch_table's own.
+// the totals kernels are launch_table's own.  p.memo (knob "pending_memo"):
+// pass 2 runs the memo kernels, except for a class whose memo kernel needs
+// more than lds_limit bytes of LDS (the plain kernel: the same results), and
+// one more launch writes the hits to probe_host[kProbePendHits].
+constexpr int kProbePendHits = 18;      // 2 slots: the pending call's memo hits, lo / hi
 hipError_t launch_table_bin(const TableArgs& p, hipStream_t s);
 hipError_t launch_table_finish(const TableArgs& p, hipStream_t s);
 hipError_t launch_table_pending(const TableArgs& p, const uint32_t grid1[3], const uint32_t grid2[3],
-                                uint32_t classes, uint8_t* assumed, hipStream_t s);
+                                uint32_t classes, uint8_t* assumed, size_t lds_limit, hipStream_t s);
 
 // The explain calls (qsmd_explain_batch): launch_table with the EXPLAIN
 // instantiations of the search kernels, which also write p.path and

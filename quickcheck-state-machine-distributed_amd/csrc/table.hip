@@ -359,8 +359,10 @@ hipError_t launch_class(const TableArgs& p, uint32_t grid, uint32_t pass2, hipSt
 size_t table_lds_bytes(const TableDev& t, int k, bool memo, bool pending) {
     const size_t ev = k == 0 ? 32 : (k == 1 ? 64 : 128);
     // (pending: csrc/tpending.hip's stack, one 32-bit level per event)
+    // (and with the memo its column of counts, one u64 per event)
     const size_t stack = pending ? ev : ev / 4;
-    return ((ev / 2 + stack + (memo ? ev : 0)) * C_LANES + (size_t)t.blob_words) * 4;
+    const size_t entry = memo ? (pending ? 2 * ev : ev) : 0;
+    return ((ev / 2 + stack + entry) * C_LANES + (size_t)t.blob_words) * 4;
 }
 
 // The first and the last launch of a table call on their own (csrc/tpending.hip).

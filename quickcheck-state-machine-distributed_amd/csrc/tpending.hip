@@ -28,7 +28,19 @@
 //   * the witness and the assumed bytes are written from the stack at the end.
 // The binning kernel, the class and heavy lists, the two passes, the totals
 // and the probe are table.hip's (launch_table_bin, launch_table_finish); the
-// memo and the explain record have no instantiation here.
+// explain record has no instantiation here.
+//
+// With the knob "pending_memo" pass 2 runs pending_search_memo: the exact-count
+// state memo of table.hip's pass 2 (TableMemo, table_lane.h)
+// under PendingDFS::step.  Below a node the search is a function of (rem,
+// state) alone -- observed or assumed is read from rem, the allowed symbols
+// from the state -- so a subtree left by a backtrack is recorded with the
+// nodes it counted and a descent of either kind into a recorded (rem, state)
+// counts them and backtracks at once.  The root rule of finish() concerns the
+// root only, which is never recorded.  The column of node counts at entry has
+// one 64-bit count per stack level, [EV][64] u64; a class whose columns and
+// tables pass the device's LDS limit runs the plain kernel in pass 2 (the
+// memo is exact: the same results).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -94,13 +106,23 @@ struct PendingDFS {
 
     // One iteration: an optional backtrack, then one child.  Returns as
     // TableDFS::step.  stk: this lane's column, level d at stk[d * C_LANES].
+    // MEMO (pass 2 with "pending_memo"): TableDFS::step<MEMO>'s rule -- the
+    // node left by a backtrack is recorded with the nodes counted below it
+    // (not when it was itself a hit), a descent of either kind probes the
+    // child's (rem, state).
+    template <bool MEMO>
     __device__ __forceinline__ int step(const TableDev& t, const PendLds& L, const uint16_t* ev, uint32_t* stk,
-                                        int lane, uint64_t limit) {
+                                        int lane, uint64_t limit, TableMemo<M>& mm) {
         const bool empty = !MO::any(cand);
         if (empty && (found == 0u || depth == 0u)) return kTerm;
         uint32_t am = 0u, j = 0u;       // the assumed symbols still to try for candidate j
         if (empty) {
             --depth;
+            if constexpr (MEMO) {
+                // (rem, state) are still the node's being left
+                if (!mm.skip) mm.record(rem, state, nodes - mm.entry[depth * C_LANES]);
+                mm.skip = false;
+            }
             const uint32_t st = stk[depth * C_LANES];
             j = st & 0xFFu;
             state = (st >> 8) & 0xFFu;
@@ -156,14 +178,31 @@ struct PendingDFS {
         rem = rem & ~MO::lowest(rem & pmj & INV);    // the pid's first remaining invocation (quirk Q1)
         cand = t_cands(rem, INV, RESP);
         found = 0u;
+        if constexpr (MEMO) {
+            mm.entry[(depth - 1u) * C_LANES] = nodes;
+            uint64_t c;
+            if (mm.probe(rem, state, c)) {
+                ++mm.hits;
+                uint64_t sum;
+                if (__builtin_add_overflow(nodes, c, &sum) || sum > limit) {   // the budget falls inside that subtree
+                    nodes = limit;
+                    return QSMD_STATUS_BUDGET;
+                }
+                nodes = sum;                         // the subtree's nodes, counted; it failed
+                cand = t_zero<M>();
+                found = 1u;
+                mm.skip = true;
+            }
+        }
         return -1;
     }
 };
 
 // table_search (table.hip) over PendingDFS; assumed: the call's assumed bytes
-// (the witness layout) or null.
-template <class M>
-__global__ __launch_bounds__(C_LANES) void pending_search(TableArgs a, uint32_t pass2, uint8_t* assumed) {
+// (the witness layout) or null.  MEMO: pass 2 with the state memo (a.memo: one
+// table of a.memo_entries entries per lane slot of the grid).
+template <class M, bool MEMO>
+__device__ __forceinline__ void pending_body(TableArgs a, uint32_t pass2, uint8_t* assumed) {
     constexpr int EV = TW<M>::EV, K = TW<M>::CLASS;
     extern __shared__ uint32_t lds[];
     const int lane = threadIdx.x;
@@ -171,10 +210,19 @@ __global__ __launch_bounds__(C_LANES) void pending_search(TableArgs a, uint32_t 
     const uint32_t total = a.cnt[(pass2 ? TC_HEAVY : TC_CLASS) + K];
     if ((uint64_t)blockIdx.x * C_LANES >= total) return;
 
-    // LDS: events [EV / 2][64] words, stack [EV][64] words, the tables
+    // LDS: events [EV / 2][64] words, stack [EV][64] words, (MEMO: the node
+    // counts at entry, [EV][64] u64,) the tables
     uint16_t* ev = reinterpret_cast<uint16_t*>(lds);
     uint32_t* stk = lds + (EV / 2) * C_LANES + lane;
-    uint32_t* tab = lds + (EV / 2 + EV) * C_LANES;
+    uint32_t* tab = lds + (EV / 2 + EV + (MEMO ? 2 * EV : 0)) * C_LANES;
+    TableMemo<M> mm;
+    if constexpr (MEMO) {
+        mm.entry = reinterpret_cast<uint64_t*>(lds + (EV / 2 + EV) * C_LANES) + lane;
+        mm.tab = a.memo + ((uint64_t)blockIdx.x * C_LANES + (uint64_t)lane) * (uint64_t)a.memo_entries * 2ull;
+        mm.mask = a.memo_entries - 1u;
+        mm.tag = a.memo_epoch << 8;
+        mm.hits = 0u;
+    }
     {
         const uint4* src = reinterpret_cast<const uint4*>(a.t.blob);
         uint4* dst = reinterpret_cast<uint4*>(tab);
@@ -210,10 +258,11 @@ __global__ __launch_bounds__(C_LANES) void pending_search(TableArgs a, uint32_t 
             status = stage_table<M>(a, H, ev, lane, dfs) ? -1 : QSMD_STATUS_ENCODE_ERROR;
             if (status == -1) dfs.init(a.state0);
         }
+        if constexpr (MEMO) mm.begin(h);
         // the time limit checked every 1024 iterations, as table_search
         while (__ballot(status == -1) != 0ull) {
             for (uint32_t k = 0; k < 1024u; ++k) {
-                if (status == -1) status = dfs.step(a.t, L, ev, stk, lane, limit);
+                if (status == -1) status = dfs.template step<MEMO>(a.t, L, ev, stk, lane, limit, mm);
                 if (__ballot(status == -1) == 0ull) break;
             }
             if (status == -1 && a.s.time_limit && __builtin_amdgcn_s_memrealtime() - t0 > a.s.time_limit) {
@@ -244,8 +293,37 @@ __global__ __launch_bounds__(C_LANES) void pending_search(TableArgs a, uint32_t 
             }
         }
         cnt.add(out, status, dfs.nodes);
+        if constexpr (MEMO) {
+            // the group's hits: one atomic per wavefront
+            const uint64_t hits = wave_sum64(mm.hits);
+            mm.hits = 0u;
+            if (lane == 0 && hits)
+                __hip_atomic_fetch_add(reinterpret_cast<unsigned long long*>(a.cnt + TC_PHITS), (unsigned long long)hits,
+                                       __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
     }
     cnt.flush(a.s.buckets, lane);
+}
+
+template <class M>
+__global__ __launch_bounds__(C_LANES) void pending_search(TableArgs a, uint32_t pass2, uint8_t* assumed) {
+    pending_body<M, false>(a, pass2, assumed);
+}
+
+// pass 2 with the state memo ("pending_memo")
+template <class M>
+__global__ __launch_bounds__(C_LANES) void pending_search_memo(TableArgs a, uint8_t* assumed) {
+    pending_body<M, true>(a, 1u, assumed);
+}
+
+// The memo call's hits for the host (table_finish's probe holds the check
+// call's, 0 here: the two knobs' counters are apart).
+__global__ void pending_hits_probe(TableArgs a) {
+    if (threadIdx.x == 0 && a.probe_host) {
+        a.probe_host[kProbePendHits] = a.cnt[TC_PHITS];
+        a.probe_host[kProbePendHits + 1] = a.cnt[TC_PHITS + 1];
+        __threadfence_system();
+    }
 }
 
 template <class M>
@@ -260,13 +338,39 @@ hipError_t launch_pending_class(const TableArgs& p, uint32_t grid, uint32_t pass
     return hipGetLastError();
 }
 
+// Pass 2 of one class with the memo; a class whose memo kernel does not fit
+// lds_limit runs the plain kernel.
+template <class M>
+hipError_t launch_pending_memo_class(const TableArgs& p, uint32_t grid, uint8_t* assumed, size_t lds_limit,
+                                     hipStream_t s) {
+    const size_t lds = table_lds_bytes(p.t, TW<M>::CLASS, true, true);
+    if (lds > lds_limit) return launch_pending_class<M>(p, grid, 1u, assumed, s);
+    if (lds > 64u * 1024u) {
+        static std::atomic<int> set[kAttrDevices];
+        const hipError_t e = ensure_dyn_lds(reinterpret_cast<const void*>(&pending_search_memo<M>), set, lds);
+        if (e != hipSuccess) return e;
+    }
+    hipLaunchKernelGGL((pending_search_memo<M>), dim3(grid), dim3(C_LANES), lds, s, p, assumed);
+    return hipGetLastError();
+}
+
 }  // namespace
 
 hipError_t launch_table_pending(const TableArgs& p, const uint32_t grid1[3], const uint32_t grid2[3],
-                                uint32_t classes, uint8_t* assumed, hipStream_t s) {
+                                uint32_t classes, uint8_t* assumed, size_t lds_limit, hipStream_t s) {
     hipError_t e = launch_table_bin(p, s);
     for (uint32_t pass2 = 0; pass2 < (p.budget ? 2u : 1u) && e == hipSuccess; ++pass2) {
         const uint32_t* g = pass2 ? grid2 : grid1;
+        if (pass2 && p.memo) {
+            if (e == hipSuccess && (classes & 1u)) e = launch_pending_memo_class<uint32_t>(p, g[0], assumed, lds_limit, s);
+            if (e == hipSuccess && (classes & 2u)) e = launch_pending_memo_class<uint64_t>(p, g[1], assumed, lds_limit, s);
+            if (e == hipSuccess && (classes & 4u)) e = launch_pending_memo_class<M128>(p, g[2], assumed, lds_limit, s);
+            if (e == hipSuccess) {
+                hipLaunchKernelGGL(pending_hits_probe, dim3(1), dim3(C_LANES), 0, s, p);
+                e = hipGetLastError();
+            }
+            continue;
+        }
         if (e == hipSuccess && (classes & 1u)) e = launch_pending_class<uint32_t>(p, g[0], pass2, assumed, s);
         if (e == hipSuccess && (classes & 2u)) e = launch_pending_class<uint64_t>(p, g[1], pass2, assumed, s);
         if (e == hipSuccess && (classes & 4u)) e = launch_pending_class<M128>(p, g[2], pass2, assumed, s);

@@ -376,6 +376,12 @@ class Context:
         "table_memo_hits_last")."""
         return self.get_param("table_memo_hits_last")
 
+    def pending_memo_hits(self):
+        """Hits of the second pass's state memo (knob "pending_memo") in the
+        most recent qsmd_check_pending_batch call; 0 when that call ran
+        without the memo (qsmd_get_param "pending_memo_hits_last")."""
+        return self.get_param("pending_memo_hits_last")
+
     def set_stage0_grid(self, max_blocks):
         self._check(self._lib.qsmd_set_stage0_grid(self._h, int(max_blocks)), "qsmd_set_stage0_grid")
 

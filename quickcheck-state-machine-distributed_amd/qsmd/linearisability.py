@@ -111,7 +111,7 @@ class CheckResult:
 
 def linearisable_batch(model, histories, model0=None, *, max_nodes=0, witness=False,
                        flags=device.QSMD_FLAG_EXHAUSTIVE, ctx=None, table_memo=None,
-                       ktable_local=None, pending=None) -> CheckResult:
+                       ktable_local=None, pending=None, pending_memo=None) -> CheckResult:
     """Check many histories in one device call.  ``table_memo`` (table models:
     entries per lane slot of the second pass's state memo, 0 = off) sets the
     context's "table_memo" knob for this call and restores it afterwards;
@@ -127,10 +127,15 @@ def linearisable_batch(model, histories, model0=None, *, max_nodes=0, witness=Fa
     invocation, with any response the model allows (qsmd_check_pending_batch,
     include/qsmd.h): with ``witness`` the result's ``assumed`` names the
     responses that were assumed.  With raise tables this can read ``error``
-    where None reads ``lin``; "table_memo" is ignored."""
+    where None reads ``lin``; "table_memo" is ignored.  ``pending_memo``
+    (only with ``pending="complete"``: entries per lane slot, 0 = off) sets the
+    pending call's own memo knob, "pending_memo", for this call and restores
+    it afterwards; every result is the plain call's."""
     m = _as_model(model)
     if pending not in (None, "complete"):
         raise ValueError('pending: None or "complete"')
+    if pending_memo is not None and not pending:
+        raise ValueError('pending_memo: only with pending="complete"')
     if pending and (not isinstance(m, TableModel) or isinstance(m, WideTableModel)):
         raise NotImplementedError('pending="complete": a TableModel only (QSMD_MODEL_TABLE)')
     batch = codec.encode(m, histories, model0)
@@ -154,6 +159,10 @@ def linearisable_batch(model, histories, model0=None, *, max_nodes=0, witness=Fa
     if ktable_local is not None and isinstance(m, KeyedTableModel):
         saved_local = ctx.get_param("ktable_local")
         ctx.set_param("ktable_local", 1 if ktable_local else 0)
+    saved_pending = None
+    if pending_memo is not None:
+        saved_pending = ctx.get_param("pending_memo")
+        ctx.set_param("pending_memo", pending_memo)
     assumed = None
     try:
         if pending:
@@ -167,16 +176,18 @@ def linearisable_batch(model, histories, model0=None, *, max_nodes=0, witness=Fa
             ctx.set_param(knob, saved)
         if saved_local is not None:
             ctx.set_param("ktable_local", saved_local)
+        if saved_pending is not None:
+            ctx.set_param("pending_memo", saved_pending)
     return CheckResult(batch, status, nodes, wit, totals, assumed=assumed)
 
 
 def linearisable(transition, postcondition, model0, history, *, max_nodes=0, ctx=None, table_memo=None,
-                 ktable_local=None, pending=None) -> bool:
+                 ktable_local=None, pending=None, pending_memo=None) -> bool:
     """``linearisable`` (src/Linearisability.hs:52-69) on the GPU
-    (``table_memo``, ``ktable_local``, ``pending``: see :func:`linearisable_batch`)."""
+    (``table_memo``, ``ktable_local``, ``pending``, ``pending_memo``: see :func:`linearisable_batch`)."""
     m = _device_model(transition, postcondition)
     res = linearisable_batch(m, [history], model0, max_nodes=max_nodes, ctx=ctx, table_memo=table_memo,
-                             ktable_local=ktable_local, pending=pending)
+                             ktable_local=ktable_local, pending=pending, pending_memo=pending_memo)
     st = int(res.status[0])
     if st == codec.STATUS_LIN:
         return True

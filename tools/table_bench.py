@@ -56,7 +56,9 @@ interleaved; a line carries "call": "check" or "explain".
 batch -- what the wider stack and the extra branch cost where nothing is
 pending -- and on the same histories with clients crashed (tests/pending_ref.py
 crash, probability 0.3 per client), the three interleaved; a line carries
-"call": "check" or "pending" and "batch": "complete" or "crash 0.3".  The
+"call": "check" or "pending" and "batch": "complete" or "crash 0.3".  With
+--memo the pending lines run with the pending call's own knob ("pending_memo",
+DESIGN.md §10j) at that size and carry "pending_memo" and "pending_memo_hits".  The
 register batch of the default run only.
 
     python tools/table_bench.py [--budgets default,0] [--memo 0,64,256,1024,4096] [--distinct 65536] [--n 1048576]
@@ -228,6 +230,8 @@ def main():
         ctx.set_param("table_memo", 0 if mid == 5 else entries)
         ctx.set_param("ktable_memo", entries if mid == 5 else 0)
         ctx.set_param("ktable_local", local)
+        # (the pending call's memo is its own knob too: "table_memo" does not reach it)
+        ctx.set_param("pending_memo", entries if call.startswith("pending") else 0)
         ms = []
         for k in range(args.warmup + args.calls):
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -259,6 +263,8 @@ def main():
             "workload": what,
             "table_budget": budget, "is_default": budget == default, "table_memo": entries,
             "memo_knob": "ktable_memo" if mid == 5 else "table_memo", "table_memo_hits": ctx.table_memo_hits(), "calls": args.calls,
+            **({"pending_memo": entries, "pending_memo_hits": ctx.pending_memo_hits()}
+               if call.startswith("pending") else {}),
             "ktable_local": local, "ktable_local_last": ctx.ktable_local_last() if mid == 5 else 0,
             "ms_per_call_median": round(med, 4), "ms_min": round(min(ms), 4), "ms_max": round(max(ms), 4),
             "histories_per_s": round(n / med * 1e3), "nodes_per_s": round(int(tot[7]) / med * 1e3),
