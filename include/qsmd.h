@@ -542,7 +542,8 @@ int qsmd_explain_batch_device(qsmd_ctx* ctx, uint32_t model_id,
  * the memo's hits in the most recent pending call (waits for it; 0 when that
  * call ran without the memo); "table_memo_hits_last" is not moved by it.
  * Models 1, 2, 4, 5 and QSMD_FLAG_EARLY_EXIT_BATCH return
- * QSMD_ERR_UNSUPPORTED. */
+ * QSMD_ERR_UNSUPPORTED (model 5 has entries of its own:
+ * qsmd_check_kpending_batch below). */
 #define QSMD_ASSUMED_NONE 0xFFu
 
 /* Host memory, synchronous (as qsmd_check_batch). */
@@ -563,6 +564,58 @@ int qsmd_check_pending_batch_device(qsmd_ctx* ctx, uint32_t model_id,
                                     uint8_t* status_dev, uint64_t* nodes_dev,
                                     uint8_t* witness_dev, qsmd_totals* totals_dev,
                                     void* stream, uint8_t* assumed_dev);
+
+/* ----------------------------------------------------------- keyed pending
+ * The same rule on the keyed table model (QSMD_MODEL_KTABLE; opt-in): the
+ * pending call for the context's keyed table (qsmd_ktable_set), new entries
+ * because qsmd_check_pending_batch keeps refusing model 5.
+ *
+ * A candidate (state vector s, invocation (k, i)) whose pid has no remaining
+ * response has one child per response symbol r, ascending, with bit r of
+ * post[s[k]][i] set and bit r of post_err[s[k]][i] clear; each is one counted
+ * node (max_nodes is tested before it) whose postcondition is not evaluated
+ * again, with s[k] := on_resp[on_inv[s[k]][i]][r] and every other key
+ * unchanged; its remaining set loses the pid's first remaining invocation and
+ * no response.  A non-empty history with no response event at all whose root
+ * has no child is LINEARISABLE with 0 nodes and an empty witness.  On a
+ * history with nothing pending, status, nodes and witness are
+ * qsmd_check_batch(QSMD_MODEL_KTABLE)'s, bit for bit.
+ *
+ * model0: n_keys uint32 states or NULL, as for the keyed check call (a state
+ * >= n_states: QSMD_ERR_ARG).  The witness and assumed layouts,
+ * QSMD_ASSUMED_NONE, the totals, the probe ("table_pass2_last") and the time
+ * limit are qsmd_check_pending_batch's; "table_budget" and max_nodes apply as
+ * for every table call; a history's ENCODE_ERROR follows the keyed check
+ * call's rules (hdr.model_id, a symbol the component does not have, a key >=
+ * n_keys).  No keyed table set: QSMD_ERR_ARG.  QSMD_FLAG_EARLY_EXIT_BATCH:
+ * QSMD_ERR_UNSUPPORTED.
+ *
+ * It is always the plain search on the product: the knobs "ktable_memo",
+ * "ktable_local", "table_memo" and "pending_memo" do not reach it, and
+ * "ktable_local_last" and "pending_memo_hits_last" are not moved by it
+ * ("table_memo_hits_last" reads 0 after it, as after qsmd_check_pending_batch
+ * without its memo).  One workgroup needs the component's tables and 12 / 24
+ * / 48 KB of LDS (32 / 64 / 128-event class): 128 KB at the largest component
+ * in the widest class. */
+
+/* Host memory, synchronous (as qsmd_check_batch). */
+int qsmd_check_kpending_batch(qsmd_ctx* ctx,
+                              const qsmd_hdr* hdr, uint64_t n_hist,
+                              const qsmd_event* events, uint64_t n_events,
+                              const void* model0, uint32_t flags, uint64_t max_nodes,
+                              uint8_t* status_out, uint64_t* nodes_out,
+                              uint8_t* witness_out, qsmd_totals* totals_out,
+                              uint8_t* assumed_out);
+
+/* Device memory, asynchronous on `stream` (as qsmd_check_batch_device). */
+int qsmd_check_kpending_batch_device(qsmd_ctx* ctx,
+                                     const qsmd_hdr* hdr_dev, uint64_t n_hist,
+                                     const qsmd_event* events_dev, uint64_t n_events,
+                                     const void* model0_host, uint32_t flags,
+                                     uint64_t max_nodes,
+                                     uint8_t* status_dev, uint64_t* nodes_dev,
+                                     uint8_t* witness_dev, qsmd_totals* totals_dev,
+                                     void* stream, uint8_t* assumed_dev);
 
 /* Safety net: a search launch whose lanes run longer than this wall time
  * stops and reports QSMD_STATUS_BUDGET for the unfinished histories (default

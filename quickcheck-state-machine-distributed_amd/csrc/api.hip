@@ -889,9 +889,12 @@ static int check_table_locked(qsmd_ctx* c, const qsmd_hdr* hdr, uint64_t n_hist,
                               hipStream_t s, uint32_t route, uint8_t* path = nullptr,
                               qsmd_explain* explain = nullptr, bool pending = false, uint8_t* assumed = nullptr) {
     constexpr bool WIDE = KIND == kTabWide, KEYED = KIND == kTabKeyed;
-    // pending: a qsmd_check_pending_batch call (model 3 only) -- the same
-    // launches with the search kernels of csrc/tpending.hip, the memo under
-    // its own knob ("pending_memo"; "table_memo" does not reach it)
+    // pending: a qsmd_check_pending_batch call (model 3) -- the same launches
+    // with the search kernels of csrc/tpending.hip, the memo under its own
+    // knob ("pending_memo"; "table_memo" does not reach it) -- or a
+    // qsmd_check_kpending_batch call (model 5) -- the keyed launches with the
+    // search kernels of csrc/kpending.hip, always the plain search on the
+    // product: no memo, no local mode, and neither mode's counters are moved
     // explain != null: a qsmd_explain_batch call -- the same launches with the
     // EXPLAIN instantiations, always the plain search on the product (no
     // memo, no local mode, no witness: the path is the witness)
@@ -930,9 +933,9 @@ static int check_table_locked(qsmd_ctx* c, const qsmd_hdr* hdr, uint64_t n_hist,
     KSplitArgs ks{};
     bool local = false;
     if constexpr (KEYED) {
-        local = c->ktable_local != 0 && !explain && !(flags & QSMD_FLAG_WITNESS) &&
+        local = c->ktable_local != 0 && !explain && !pending && !(flags & QSMD_FLAG_WITNESS) &&
                 n_hist * (uint64_t)c->ktab_keys <= 0xFFFFFFFFull;
-        c->ktable_local_call = local;
+        if (!pending) c->ktable_local_call = local;
         if (local) {
             const uint64_t n_sub = n_hist * c->ktab_keys;
             const size_t o_bk = 256;
@@ -1040,10 +1043,11 @@ static int check_table_locked(qsmd_ctx* c, const qsmd_hdr* hdr, uint64_t n_hist,
     // ("ktable_memo"; "table_memo" does not reach it, nor "ktable_memo" the
     // other two), 48-byte entries and full-word epochs; its sizing is
     // ktable_memo_plan (ktable_host.h).  A pending call ("pending_memo") uses
-    // the narrow path's tables, sizing and epochs.
+    // the narrow path's tables, sizing and epochs; a keyed pending call has
+    // no memo.
     const uint64_t memo_entries =
-        explain ? 0 : (pending ? c->pending_memo : (KEYED ? c->ktable_memo : c->table_memo));
-    if (pending) c->pending_memo_call = memo_entries && c->table_budget;
+        explain ? 0 : (pending ? (KEYED ? 0 : c->pending_memo) : (KEYED ? c->ktable_memo : c->table_memo));
+    if (pending && !KEYED) c->pending_memo_call = memo_entries && c->table_budget;
     if (memo_entries && c->table_budget) {
         uint64_t gm;
         size_t need;
@@ -1096,6 +1100,9 @@ static int check_table_locked(qsmd_ctx* c, const qsmd_hdr* hdr, uint64_t n_hist,
             HIP_TRY(c,
                     launch_table_pending(p, grid1, grid2, classes, p.s.witness ? assumed : nullptr, c->lds_limit, s),
                     "table pending launch");
+        if constexpr (KEYED)
+            HIP_TRY(c, launch_ktable_pending(p, grid1, grid2, classes, p.s.witness ? assumed : nullptr, s),
+                    "keyed table pending launch");
     } else if (explain) {
         HIP_TRY(c, launch_explain_prepare(p.s, (uint64_t)state0, path, p.explain, s), "explain prepare launch");
         HIP_TRY(c, launch_table_explain(p, grid1, grid2, classes, s), "table explain launch");
@@ -1721,6 +1728,17 @@ static int pending_device_locked(qsmd_ctx* c, uint32_t model_id, const qsmd_hdr*
                                           witness, totals, s, route, nullptr, nullptr, true, assumed);
 }
 
+// qsmd_check_kpending_batch's route: the context's keyed table (model 5), through
+// check_table_locked with the search kernels of csrc/kpending.hip.  (The
+// model id is the entry's own: the signature is pending_device_locked's.)
+static int kpending_device_locked(qsmd_ctx* c, uint32_t, const qsmd_hdr* hdr, uint64_t n_hist,
+                                  const qsmd_event* events, uint64_t n_events, const void* model0, uint32_t flags,
+                                  uint64_t max_nodes, uint8_t* status, uint64_t* nodes, uint8_t* witness,
+                                  uint8_t* assumed, qsmd_totals* totals, hipStream_t s, uint32_t route) {
+    return check_table_locked<kTabKeyed>(c, hdr, n_hist, events, n_events, model0, flags, max_nodes, status, nodes,
+                                         witness, totals, s, route, nullptr, nullptr, true, assumed);
+}
+
 int qsmd_check_pending_batch_device(qsmd_ctx* c, uint32_t model_id, const qsmd_hdr* hdr_dev, uint64_t n_hist,
                                     const qsmd_event* events_dev, uint64_t n_events, const void* model0_host,
                                     uint32_t flags, uint64_t max_nodes, uint8_t* status_dev, uint64_t* nodes_dev,
@@ -1734,10 +1752,11 @@ int qsmd_check_pending_batch_device(qsmd_ctx* c, uint32_t model_id, const qsmd_h
                                  status_dev, nodes_dev, witness_dev, assumed_dev, totals_dev, s, 0u);
 }
 
-int qsmd_check_pending_batch(qsmd_ctx* c, uint32_t model_id, const qsmd_hdr* hdr, uint64_t n_hist,
-                             const qsmd_event* events, uint64_t n_events, const void* model0, uint32_t flags,
-                             uint64_t max_nodes, uint8_t* status_out, uint64_t* nodes_out, uint8_t* witness_out,
-                             qsmd_totals* totals_out, uint8_t* assumed_out) {
+// The host entry of both pending calls (keyed: qsmd_check_kpending_batch).
+static int pending_host(qsmd_ctx* c, bool keyed, uint32_t model_id, const qsmd_hdr* hdr, uint64_t n_hist,
+                        const qsmd_event* events, uint64_t n_events, const void* model0, uint32_t flags,
+                        uint64_t max_nodes, uint8_t* status_out, uint64_t* nodes_out, uint8_t* witness_out,
+                        qsmd_totals* totals_out, uint8_t* assumed_out) {
     if (!c) return QSMD_ERR_ARG;
     if (n_hist && (!hdr || !status_out)) return fail(c, QSMD_ERR_ARG, "null hdr/status");
     if (n_events && !events) return fail(c, QSMD_ERR_ARG, "null events");
@@ -1770,12 +1789,12 @@ int qsmd_check_pending_batch(qsmd_ctx* c, uint32_t model_id, const qsmd_hdr* hdr
     uint32_t route = kClassesKnown;         // the width classes present (one launch per non-empty class)
     for (uint64_t i = 0; i < n_hist && (route & 7u) != 7u; ++i)
         route |= hdr[i].n_ev <= 32u ? 1u : (hdr[i].n_ev <= 64u ? 2u : 4u);
-    rc = pending_device_locked(c, model_id, reinterpret_cast<qsmd_hdr*>(c->io + o_hdr), n_hist,
-                               reinterpret_cast<qsmd_event*>(c->io + o_ev), n_events, model0, flags, max_nodes,
-                               reinterpret_cast<uint8_t*>(c->io + o_st), reinterpret_cast<uint64_t*>(c->io + o_nd),
-                               want_w ? reinterpret_cast<uint8_t*>(c->io + o_w) : nullptr,
-                               want_a ? reinterpret_cast<uint8_t*>(c->io + o_a) : nullptr,
-                               reinterpret_cast<qsmd_totals*>(c->io + o_tot), s, route);
+    rc = (keyed ? kpending_device_locked : pending_device_locked)(
+        c, model_id, reinterpret_cast<qsmd_hdr*>(c->io + o_hdr), n_hist, reinterpret_cast<qsmd_event*>(c->io + o_ev),
+        n_events, model0, flags, max_nodes, reinterpret_cast<uint8_t*>(c->io + o_st),
+        reinterpret_cast<uint64_t*>(c->io + o_nd), want_w ? reinterpret_cast<uint8_t*>(c->io + o_w) : nullptr,
+        want_a ? reinterpret_cast<uint8_t*>(c->io + o_a) : nullptr, reinterpret_cast<qsmd_totals*>(c->io + o_tot), s,
+        route);
     if (rc) {
         (void)hipStreamSynchronize(s);      // (the copy in may still read the pinned buffer)
         return rc;
@@ -1789,6 +1808,35 @@ int qsmd_check_pending_batch(qsmd_ctx* c, uint32_t model_id, const qsmd_hdr* hdr
     if (want_a) std::memcpy(assumed_out, c->pin + o_a, n_events);
     if (totals_out) std::memcpy(totals_out, c->pin + o_tot, sizeof(qsmd_totals));
     return QSMD_OK;
+}
+
+int qsmd_check_pending_batch(qsmd_ctx* c, uint32_t model_id, const qsmd_hdr* hdr, uint64_t n_hist,
+                             const qsmd_event* events, uint64_t n_events, const void* model0, uint32_t flags,
+                             uint64_t max_nodes, uint8_t* status_out, uint64_t* nodes_out, uint8_t* witness_out,
+                             qsmd_totals* totals_out, uint8_t* assumed_out) {
+    return pending_host(c, false, model_id, hdr, n_hist, events, n_events, model0, flags, max_nodes, status_out,
+                        nodes_out, witness_out, totals_out, assumed_out);
+}
+
+int qsmd_check_kpending_batch(qsmd_ctx* c, const qsmd_hdr* hdr, uint64_t n_hist, const qsmd_event* events,
+                              uint64_t n_events, const void* model0, uint32_t flags, uint64_t max_nodes,
+                              uint8_t* status_out, uint64_t* nodes_out, uint8_t* witness_out,
+                              qsmd_totals* totals_out, uint8_t* assumed_out) {
+    return pending_host(c, true, QSMD_MODEL_KTABLE, hdr, n_hist, events, n_events, model0, flags, max_nodes,
+                        status_out, nodes_out, witness_out, totals_out, assumed_out);
+}
+
+int qsmd_check_kpending_batch_device(qsmd_ctx* c, const qsmd_hdr* hdr_dev, uint64_t n_hist,
+                                     const qsmd_event* events_dev, uint64_t n_events, const void* model0_host,
+                                     uint32_t flags, uint64_t max_nodes, uint8_t* status_dev, uint64_t* nodes_dev,
+                                     uint8_t* witness_dev, qsmd_totals* totals_dev, void* stream,
+                                     uint8_t* assumed_dev) {
+    if (!c) return QSMD_ERR_ARG;
+    std::lock_guard<std::mutex> g(c->mu);
+    hipStream_t s = stream ? static_cast<hipStream_t>(stream) : ctx_stream(c);
+    if (!s) return fail(c, QSMD_ERR_DEVICE, "hipStreamCreate");
+    return kpending_device_locked(c, QSMD_MODEL_KTABLE, hdr_dev, n_hist, events_dev, n_events, model0_host, flags,
+                                  max_nodes, status_dev, nodes_dev, witness_dev, assumed_dev, totals_dev, s, 0u);
 }
 
 static int wellformed_locked(qsmd_ctx* c, const qsmd_hdr* hdr, uint64_t n_hist, const qsmd_event* events,

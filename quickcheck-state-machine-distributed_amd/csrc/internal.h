@@ -531,6 +531,17 @@ hipError_t launch_table(const KTableArgs& p, const uint32_t grid1[3], const uint
 hipError_t launch_table_explain(const KTableArgs& p, const uint32_t grid1[3], const uint32_t grid2[3],
                                 uint32_t classes, hipStream_t s);
 
+// qsmd_check_kpending_batch (csrc/kpending.hip): the keyed launch_table's
+// launches with the search kernels that let a pending invocation take effect
+// on the product; assumed: the call's assumed bytes (device, the witness
+// layout) or null.  The binning and the totals kernels are the keyed
+// launch_table's own.  Always the plain search: p.memo is not read.  One
+// workgroup's LDS is table_lds_bytes(p.t, k, false, true).
+hipError_t launch_ktable_bin(const KTableArgs& p, hipStream_t s);
+hipError_t launch_ktable_finish(const KTableArgs& p, hipStream_t s);
+hipError_t launch_ktable_pending(const KTableArgs& p, const uint32_t grid1[3], const uint32_t grid2[3],
+                                 uint32_t classes, uint8_t* assumed, hipStream_t s);
+
 // QSMD_MODEL_KTABLE's local mode (csrc/ksplit.hip, knob "ktable_local"): the
 // split kernel writes n_keys sub-headers per history (slot h * n_keys + k) and
 // the events grouped by key into the context's workspace, launch_table

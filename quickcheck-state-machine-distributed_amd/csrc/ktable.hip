@@ -23,7 +23,8 @@
 //   * an event stays 16 bits in LDS: pid 7 | kind 1 | code 5 | key 3 (the
 //     component has at most 32 symbols; a response's key bits are 0), in
 //     col16's paired words, so the per-lane indexed reads of a divergent
-//     wavefront stay conflict-free and the LDS bytes are model 3's.
+//     wavefront stay conflict-free and the LDS bytes are model 3's (the
+//     element and its staging: ktable_lane.h, shared with kpending.hip).
 //
 // Pass 2's exact-count state memo (knob "ktable_memo") is
 // table.hip's rule (TableDFS::step<MEMO>) on S = (rem, the full 64-bit
@@ -50,6 +51,7 @@
 #include <algorithm>
 
 #include "internal.h"
+#include "ktable_lane.h"
 #include "lane.h"
 #include "mask.h"
 #include "table_lane.h"
@@ -59,6 +61,7 @@ namespace qsmd {
 namespace {
 
 using namespace tlane;
+using namespace klane;
 
 struct KTabLds {
     const uint32_t* post;
@@ -66,10 +69,6 @@ struct KTabLds {
     const uint8_t* on_inv;
     const uint8_t* on_resp;
 };
-
-// the staged event: its symbol, its key (invocations)
-__device__ __forceinline__ uint32_t kev_code(uint32_t e) { return (e >> 8) & 31u; }
-__device__ __forceinline__ uint32_t kev_key(uint32_t e) { return e >> 13; }
 
 // One lane's view of pass 2's state memo (the header comment): its table in
 // HBM, its LDS column of node counts at entry per level, the map of written
@@ -251,55 +250,6 @@ struct KTableDFS {
     }
 };
 
-// tlane::stage_table for keyed events: the 16-bit LDS element is pid 7 |
-// kind 1 | code 5 | key 3, and an invocation's key must be < n_keys.
-template <class M>
-__device__ __forceinline__ bool stage_ktable(const KTableArgs& a, const qsmd_hdr& H, uint16_t* ev, int lane,
-                                             KTableDFS<M>& dfs) {
-    constexpr int NW = TW<M>::NW;
-    const uint32_t n_ev = H.n_ev;
-    const uint2* evp = a.s.events + H.ev_off;
-    const uint32_t last = n_ev - 1u;                 // (n_ev >= 1: the binning kernel)
-    uint32_t pl[8][NW];
-#pragma unroll
-    for (int b = 0; b < 8; ++b)
-#pragma unroll
-        for (int q = 0; q < NW; ++q) pl[b][q] = 0u;
-    uint32_t bad = 0u;
-#pragma unroll
-    for (int q = 0; q < NW; ++q) {
-#pragma unroll 1
-        for (uint32_t c0 = 0; c0 < 32u; c0 += 8u) {
-            const uint32_t e0 = (uint32_t)q * 32u + c0;
-            if (e0 >= n_ev) break;
-            uint32_t x[8];
-#pragma unroll
-            for (uint32_t k = 0; k < 8u; ++k) x[k] = evp[min(e0 + k, last)].x;
-#pragma unroll
-            for (uint32_t k = 0; k < 8u; ++k) {
-                const uint32_t e = e0 + k;
-                const bool in = e < n_ev;
-                const uint32_t lo = x[k];
-                const bool resp = (lo & QSMD_EV_RESP) != 0u;
-                const uint32_t code = (lo >> 8) & 0xFFu, key = resp ? 0u : (lo >> 16) & 0xFFu;
-                if (in) ev[col16(e, lane)] = (uint16_t)((lo & 0xFFu) | ((code & 31u) << 8) | ((key & 7u) << 13));
-                const uint32_t bit = in ? 1u << (c0 + k) : 0u;
-#pragma unroll
-                for (int b = 0; b < 8; ++b) pl[b][q] |= ((lo >> b) & 1u) ? bit : 0u;
-                bad |= (in && (code >= (resp ? a.t.n_resp : a.t.n_inv) || key >= a.n_keys)) ? 1u : 0u;
-            }
-        }
-    }
-    const M ALL = MaskOps<M>::below((int)n_ev);
-    M resp;
-    from_words(pl[7], resp);
-    dfs.RESP = resp & ALL;
-    dfs.INV = ALL & ~resp;
-#pragma unroll
-    for (int b = 0; b < 7; ++b) from_words(pl[b], dfs.P[b]);
-    return bad == 0u;
-}
-
 // Sort the headers into the three class lists; the histories decided from
 // the header alone get their result here.
 __global__ __launch_bounds__(C_LANES) void ktable_bin(KTableArgs a) {
@@ -467,11 +417,21 @@ hipError_t launch_class(const KTableArgs& p, uint32_t grid, uint32_t pass2, hipS
 
 }  // namespace
 
-hipError_t launch_table(const KTableArgs& p, const uint32_t grid1[3], const uint32_t grid2[3], uint32_t classes,
-                        hipStream_t s) {
+// The first and the last launch of a keyed call on their own (csrc/kpending.hip).
+hipError_t launch_ktable_bin(const KTableArgs& p, hipStream_t s) {
     const uint32_t gb = (uint32_t)std::min<uint64_t>(std::max<uint64_t>((p.s.n_hist + 63) / 64, 1), 4096);
     hipLaunchKernelGGL(ktable_bin, dim3(gb), dim3(C_LANES), 0, s, p);
-    hipError_t e = hipGetLastError();
+    return hipGetLastError();
+}
+
+hipError_t launch_ktable_finish(const KTableArgs& p, hipStream_t s) {
+    hipLaunchKernelGGL(ktable_finish, dim3(1), dim3(C_LANES), 0, s, p);
+    return hipGetLastError();
+}
+
+hipError_t launch_table(const KTableArgs& p, const uint32_t grid1[3], const uint32_t grid2[3], uint32_t classes,
+                        hipStream_t s) {
+    hipError_t e = launch_ktable_bin(p, s);
     for (uint32_t pass2 = 0; pass2 < (p.budget ? 2u : 1u) && e == hipSuccess; ++pass2) {
         const uint32_t* g = pass2 ? grid2 : grid1;
         if (pass2 && p.memo) {
@@ -485,8 +445,7 @@ hipError_t launch_table(const KTableArgs& p, const uint32_t grid1[3], const uint
         if (e == hipSuccess && (classes & 4u)) e = launch_class<M128, false>(p, g[2], pass2, s);
     }
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(ktable_finish, dim3(1), dim3(C_LANES), 0, s, p);
-    return hipGetLastError();
+    return launch_ktable_finish(p, s);
 }
 
 // The explain call's launches (include/qsmd.h qsmd_explain_batch): launch_table

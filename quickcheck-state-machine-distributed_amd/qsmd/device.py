@@ -84,6 +84,8 @@ EXPORTS = {
     "qsmd_explain_batch_device": (_I, [_P, _U32, _P, _U64, _P, _U64, _P, _U32, _U64, _P, _P, _P, _P, _P, _P]),
     "qsmd_check_pending_batch": (_I, [_P, _U32, _P, _U64, _P, _U64, _P, _U32, _U64, _P, _P, _P, _P, _P]),
     "qsmd_check_pending_batch_device": (_I, [_P, _U32, _P, _U64, _P, _U64, _P, _U32, _U64, _P, _P, _P, _P, _P, _P]),
+    "qsmd_check_kpending_batch": (_I, [_P, _P, _U64, _P, _U64, _P, _U32, _U64, _P, _P, _P, _P, _P]),
+    "qsmd_check_kpending_batch_device": (_I, [_P, _P, _U64, _P, _U64, _P, _U32, _U64, _P, _P, _P, _P, _P, _P]),
     "qsmd_last_kernel_ms": (_I, [_P, ctypes.POINTER(ctypes.c_float)]),
     "qsmd_timing_reset": (_I, [_P]),
     "qsmd_timing_read": (_I, [_P, _P, _P, _U64, ctypes.POINTER(_U64)]),
@@ -268,6 +270,44 @@ class Context:
             self._h, model_id, hdr_ptr, n_hist, events_ptr, n_events, m0, flags, max_nodes,
             status_ptr, nodes_ptr, witness_ptr, totals_ptr, stream, assumed_ptr)
         self._check(rc, "qsmd_check_pending_batch_device")
+
+    def check_kpending_arrays(self, hdr, events, model0=None, flags=QSMD_FLAG_EXHAUSTIVE, max_nodes=0,
+                              witness=False):
+        """qsmd_check_kpending_batch on a host-memory batch: the keyed check
+        call (QSMD_MODEL_KTABLE, the context's keyed table) with pending
+        invocations allowed to take effect.  ``model0``: ``n_keys`` uint32
+        states (a ctypes array) or None.  Returns as
+        :meth:`check_pending_arrays`: (status, nodes, witness, assumed,
+        totals)."""
+        hdr = np.ascontiguousarray(hdr, dtype=codec.HDR_DTYPE)
+        events = np.ascontiguousarray(events, dtype=codec.EV_DTYPE)
+        n = len(hdr)
+        status = np.empty(n, dtype=np.uint8)
+        nodes = np.empty(n, dtype=np.uint64)
+        wit = np.full(len(events), 0xFF, dtype=np.uint8) if witness else None
+        assumed = np.full(len(events), QSMD_ASSUMED_NONE, dtype=np.uint8) if witness else None
+        if witness:
+            flags |= QSMD_FLAG_WITNESS
+        tot = Totals()
+        m0 = ctypes.cast(ctypes.pointer(model0), ctypes.c_void_p) if model0 is not None else None
+        rc = self._lib.qsmd_check_kpending_batch(
+            self._h, _ptr(hdr) if n else None, n,
+            _ptr(events) if len(events) else None, len(events), m0, flags, max_nodes,
+            _ptr(status) if n else None, _ptr(nodes) if n else None,
+            _ptr(wit) if (wit is not None and len(events)) else None, ctypes.byref(tot),
+            _ptr(assumed) if (assumed is not None and len(events)) else None)
+        self._check(rc, "qsmd_check_kpending_batch")
+        return status, nodes, wit, assumed, tot.as_dict()
+
+    def check_kpending_device(self, hdr_ptr, n_hist, events_ptr, n_events, status_ptr,
+                              nodes_ptr=None, witness_ptr=None, totals_ptr=None, model0=None,
+                              flags=QSMD_FLAG_EXHAUSTIVE, max_nodes=0, stream=None, assumed_ptr=None):
+        """qsmd_check_kpending_batch_device: raw device pointers (ints), async on stream."""
+        m0 = ctypes.cast(ctypes.pointer(model0), ctypes.c_void_p) if model0 is not None else None
+        rc = self._lib.qsmd_check_kpending_batch_device(
+            self._h, hdr_ptr, n_hist, events_ptr, n_events, m0, flags, max_nodes,
+            status_ptr, nodes_ptr, witness_ptr, totals_ptr, stream, assumed_ptr)
+        self._check(rc, "qsmd_check_kpending_batch_device")
 
     def explain_arrays(self, model_id, hdr, events, model0=None, flags=QSMD_FLAG_EXHAUSTIVE, max_nodes=0,
                        path=None):

@@ -121,23 +121,30 @@ def linearisable_batch(model, histories, model0=None, *, max_nodes=0, witness=Fa
     this call in the same way -- every splittable history is then checked key
     by key (include/qsmd.h; :meth:`KeyedTableModel.split_history`).
 
-    ``pending`` (a :class:`TableModel` only): None is the reference's rule --
-    an invocation that never got its response is an operation that never
-    happened.  ``"complete"`` also lets it take effect, at any point after its
-    invocation, with any response the model allows (qsmd_check_pending_batch,
+    ``pending`` (a :class:`TableModel` or a :class:`KeyedTableModel`): None is
+    the reference's rule -- an invocation that never got its response is an
+    operation that never happened.  ``"complete"`` also lets it take effect,
+    at any point after its invocation, with any response the model allows
+    (qsmd_check_pending_batch, for a keyed model qsmd_check_kpending_batch,
     include/qsmd.h): with ``witness`` the result's ``assumed`` names the
     responses that were assumed.  With raise tables this can read ``error``
-    where None reads ``lin``; "table_memo" is ignored.  ``pending_memo``
-    (only with ``pending="complete"``: entries per lane slot, 0 = off) sets the
-    pending call's own memo knob, "pending_memo", for this call and restores
-    it afterwards; every result is the plain call's."""
+    where None reads ``lin``; "table_memo" is ignored, and for a keyed model
+    so are "ktable_memo" and "ktable_local" (the plain search on the product).
+    ``pending_memo`` (only with ``pending="complete"`` and a
+    :class:`TableModel`: entries per lane slot, 0 = off) sets the pending
+    call's own memo knob, "pending_memo", for this call and restores it
+    afterwards; every result is the plain call's."""
     m = _as_model(model)
     if pending not in (None, "complete"):
         raise ValueError('pending: None or "complete"')
     if pending_memo is not None and not pending:
         raise ValueError('pending_memo: only with pending="complete"')
-    if pending and (not isinstance(m, TableModel) or isinstance(m, WideTableModel)):
-        raise NotImplementedError('pending="complete": a TableModel only (QSMD_MODEL_TABLE)')
+    keyed = isinstance(m, KeyedTableModel)
+    if pending and not keyed and (not isinstance(m, TableModel) or isinstance(m, WideTableModel)):
+        raise NotImplementedError('pending="complete": a TableModel or a KeyedTableModel only '
+                                  '(QSMD_MODEL_TABLE, QSMD_MODEL_KTABLE)')
+    if pending_memo is not None and keyed:
+        raise ValueError("pending_memo: the keyed pending call has no memo")
     batch = codec.encode(m, histories, model0)
     accounts0 = m.new_account_map(model0)
     packed = m.pack_model0(model0, accounts0)
@@ -165,7 +172,10 @@ def linearisable_batch(model, histories, model0=None, *, max_nodes=0, witness=Fa
         ctx.set_param("pending_memo", pending_memo)
     assumed = None
     try:
-        if pending:
+        if pending and keyed:
+            status, nodes, wit, assumed, totals = ctx.check_kpending_arrays(batch.hdr, batch.events, packed, flags,
+                                                                            max_nodes, witness)
+        elif pending:
             status, nodes, wit, assumed, totals = ctx.check_pending_arrays(m.model_id, batch.hdr, batch.events,
                                                                            packed, flags, max_nodes, witness)
         else:
@@ -322,18 +332,22 @@ def wellformed(pids, history):
 # ---------------------------------------------------------------------------
 
 def _replay_pending(m, history, witness, model0, assumed) -> bool:
-    """:func:`replay_witness` under ``pending="complete"`` (a TableModel):
-    ``assumed[d]`` is None for an observed level, else the index of the
-    response symbol assumed there."""
+    """:func:`replay_witness` under ``pending="complete"`` (a TableModel or a
+    KeyedTableModel): ``assumed[d]`` is None for an observed level, else the
+    index of the response symbol assumed there."""
     if len(assumed) != len(witness):
         return False
     cur = m.init_model if model0 is None else model0
     removed = set()
 
     def allowed(state, inv):
-        s, i = m._state(state), m.encode_inv(inv, None)[0]
-        err = 0 if m.post_err is None else int(m.post_err[s, i])
-        return int(m.post[s, i]) & ~err & ((1 << len(m.resps)) - 1)
+        t = m
+        if isinstance(m, KeyedTableModel):      # the component's tables at that key's state
+            k, inv = m._split(inv)
+            t, state = m.component, m._model(state)[k]
+        s, i = t._state(state), t.encode_inv(inv, None)[0]
+        err = 0 if t.post_err is None else int(t.post_err[s, i])
+        return int(t.post[s, i]) & ~err & ((1 << len(t.resps)) - 1)
 
     for j, a in zip(witness, assumed):
         if not 0 <= j < len(history) or j in removed or history[j][1][0] != "L":
@@ -376,7 +390,8 @@ def replay_witness(model, history, witness, model0=None, assumed=None) -> bool:
     first remaining invocation and response of that pid (Lemma L1).  True iff
     every postcondition holds and the final state has no further child.
 
-    ``assumed`` (``pending="complete"``, a :class:`TableModel`): one entry
+    ``assumed`` (``pending="complete"``, a :class:`TableModel` or a
+    :class:`KeyedTableModel`): one entry
     per level, None for an observed response or the index of the response
     symbol assumed there (:meth:`CheckResult.assumed_of`).  An assumed level is
     replayed with the named response: its pid must have no remaining response

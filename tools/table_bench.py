@@ -59,7 +59,10 @@ crash, probability 0.3 per client), the three interleaved; a line carries
 "call": "check" or "pending" and "batch": "complete" or "crash 0.3".  With
 --memo the pending lines run with the pending call's own knob ("pending_memo",
 DESIGN.md §10j) at that size and carry "pending_memo" and "pending_memo_hits".  The
-register batch of the default run only.
+register batch of the default run, or with --keyed K the keyed batch above as
+QSMD_MODEL_KTABLE alone (no flat product): the keyed check call against
+qsmd_check_kpending_batch_device (csrc/kpending.hip), which has
+no memo and no local mode -- --memo sizes the check lines only, --local stays 0.
 
     python tools/table_bench.py [--budgets default,0] [--memo 0,64,256,1024,4096] [--distinct 65536] [--n 1048576]
                                 [--wide 0|1|both] [--model register|kv] [--generated] [--seed S] [--keyed K]
@@ -106,8 +109,10 @@ def main():
     ap.add_argument("--explain", action="store_true")
     ap.add_argument("--pending", action="store_true")
     args = ap.parse_args()
-    if args.pending and (args.generated or args.keyed or args.wide != "0" or args.model != "register" or args.explain):
-        ap.error("--pending runs the register batch of the default run alone")
+    if args.pending and (args.generated or args.wide != "0" or args.model != "register" or args.explain):
+        ap.error("--pending runs the register batch of the default run (or of --keyed K) alone")
+    if args.pending and args.keyed and args.local != "0":
+        ap.error("--pending: the keyed pending call has no local mode")
     if args.local != "0" and not args.keyed:
         ap.error("--local is the keyed path's (--keyed K)")
     if (args.clients, args.ops, args.p_bug) != (4, 16, 0.39) and not args.generated:
@@ -139,8 +144,10 @@ def main():
         import ktablegen as kg
         km = KeyedTableModel(m, args.keyed)
         ctx.set_keyed_table(km)
-        if args.generated:
+        if args.generated or args.pending:
             ids, encoders = [5], {5: km}
+            if args.keyed > 1 and not args.generated:
+                model = kg.product(model, args.keyed)
         elif args.keyed == 1:
             ids, encoders = [3, 5], {3: m, 5: km}
         else:
@@ -183,11 +190,13 @@ def main():
     else:
         rng = random.Random("table_bench")
         hists = [tg.gen_history(model, rng, 4, 16, 0.03) for _ in range(args.distinct)]
-        for mid in ids:                     # the same histories, in each model's encoding
-            hs = hists
+        def encoded(mid, hs):               # the histories in a model's encoding
             if args.keyed == 1 and mid == 5:        # the one key
-                hs = [[(p, (k, (0, x) if k == "L" else x)) for p, (k, x) in h] for h in hists]
-            batch = codec.encode(encoders[mid], hs)
+                hs = [[(p, (k, (0, x) if k == "L" else x)) for p, (k, x) in h] for h in hs]
+            return codec.encode(encoders[mid], hs)
+
+        for mid in ids:                     # the same histories, in each model's encoding
+            batch = encoded(mid, hists)
             assert not batch.encode_errors
             per = len(batch.events)
             hdr = np.tile(batch.hdr, reps)
@@ -201,12 +210,13 @@ def main():
         if args.pending:                    # the same histories with clients crashed, tiled alike
             import pending_ref
             crash_rng = random.Random("table_bench/crash")
-            batch = codec.encode(m, [pending_ref.crash(h, crash_rng, 0.3) for h in hists])
+            batch = encoded(ids[0], [pending_ref.crash(h, crash_rng, 0.3) for h in hists])
             assert not batch.encode_errors
             per_c = len(batch.events)
             hdr = np.tile(batch.hdr, reps)
             hdr["ev_off"] = (hdr["ev_off"].astype(np.int64) + np.repeat(np.arange(reps, dtype=np.int64) * per_c,
                                                                          args.distinct)).astype(np.uint32)
+            hdr["model_id"] = ids[0]
             d_hdr_c = torch.from_numpy(hdr.view(np.uint8).copy()).to(dev)
             d_ev_c = torch.from_numpy(np.tile(batch.events, reps).view(np.uint8)).to(dev)
             n_events_c = per_c * reps
@@ -228,10 +238,10 @@ def main():
         ctx.set_param("table_budget", budget)
         # (the keyed path's memo has its own knob; each knob is set for its own path alone)
         ctx.set_param("table_memo", 0 if mid == 5 else entries)
-        ctx.set_param("ktable_memo", entries if mid == 5 else 0)
+        ctx.set_param("ktable_memo", entries if mid == 5 and call == "check" else 0)
         ctx.set_param("ktable_local", local)
         # (the pending call's memo is its own knob too: "table_memo" does not reach it)
-        ctx.set_param("pending_memo", entries if call.startswith("pending") else 0)
+        ctx.set_param("pending_memo", entries if call.startswith("pending") and mid != 5 else 0)
         ms = []
         for k in range(args.warmup + args.calls):
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -240,14 +250,15 @@ def main():
                 ctx.explain_device(mid, d_hdr.data_ptr(), n, d_ev.data_ptr(), n_events, d_st.data_ptr(),
                                    d_path.data_ptr(), d_rec.data_ptr(), d_nd.data_ptr(), d_tot.data_ptr(),
                                    max_nodes=args.max_nodes, stream=stream)
-            elif call == "pending":
-                ctx.check_pending_device(mid, d_hdr.data_ptr(), n, d_ev.data_ptr(), n_events, d_st.data_ptr(),
-                                         d_nd.data_ptr(), None, d_tot.data_ptr(), max_nodes=args.max_nodes,
-                                         stream=stream)
-            elif call == "pending/crash":
-                ctx.check_pending_device(mid, d_hdr_c.data_ptr(), n, d_ev_c.data_ptr(), n_events_c, d_st.data_ptr(),
-                                         d_nd.data_ptr(), None, d_tot.data_ptr(), max_nodes=args.max_nodes,
-                                         stream=stream)
+            elif call.startswith("pending"):
+                hp, ep, ne = ((d_hdr_c, d_ev_c, n_events_c) if call == "pending/crash" else (d_hdr, d_ev, n_events))
+                if mid == 5:
+                    ctx.check_kpending_device(hp.data_ptr(), n, ep.data_ptr(), ne, d_st.data_ptr(), d_nd.data_ptr(),
+                                              None, d_tot.data_ptr(), max_nodes=args.max_nodes, stream=stream)
+                else:
+                    ctx.check_pending_device(mid, hp.data_ptr(), n, ep.data_ptr(), ne, d_st.data_ptr(),
+                                             d_nd.data_ptr(), None, d_tot.data_ptr(), max_nodes=args.max_nodes,
+                                             stream=stream)
             else:
                 ctx.check_device(mid, d_hdr.data_ptr(), n, d_ev.data_ptr(), n_events, d_st.data_ptr(),
                                  d_nd.data_ptr(), None, d_tot.data_ptr(), max_nodes=args.max_nodes, stream=stream)
@@ -264,7 +275,7 @@ def main():
             "table_budget": budget, "is_default": budget == default, "table_memo": entries,
             "memo_knob": "ktable_memo" if mid == 5 else "table_memo", "table_memo_hits": ctx.table_memo_hits(), "calls": args.calls,
             **({"pending_memo": entries, "pending_memo_hits": ctx.pending_memo_hits()}
-               if call.startswith("pending") else {}),
+               if call.startswith("pending") and mid != 5 else {}),
             "ktable_local": local, "ktable_local_last": ctx.ktable_local_last() if mid == 5 else 0,
             "ms_per_call_median": round(med, 4), "ms_min": round(min(ms), 4), "ms_max": round(max(ms), 4),
             "histories_per_s": round(n / med * 1e3), "nodes_per_s": round(int(tot[7]) / med * 1e3),
