@@ -162,6 +162,8 @@ typedef struct qsmd_bank_model {
  * table call (waits for it).  The cascade's knobs, qsmd_probe_read and the
  * timing ring (qsmd_last_kernel_ms, qsmd_timing_read) do not apply to table
  * calls. */
+/* Bits of post / post_err at or above n_resp are ignored by every entry, the
+ * pending ones (qsmd_check_pending_batch, qsmd_check_kpending_batch) included. */
 #define QSMD_MODEL_TABLE 3u
 #define QSMD_TABLE_MAX_STATES 256
 #define QSMD_TABLE_MAX_INV     32
@@ -197,7 +199,8 @@ typedef struct qsmd_table_model {
  * table's n_states / n_inv / n_resp, and qsmd_wtable_set in place of
  * qsmd_table_set.  The knobs "table_budget", "table_memo", "table_memo_grid"
  * and the read-outs "table_pass2_last", "table_memo_hits_last" apply
- * unchanged.  A context holds one narrow and one wide table, independently. */
+ * unchanged.  A context holds one narrow and one wide table, independently.
+ * Bits of the last post / post_err word at or above n_resp are ignored. */
 #define QSMD_MODEL_WTABLE 4u
 #define QSMD_WTABLE_MAX_STATES 65536
 #define QSMD_WTABLE_MAX_INV      256
