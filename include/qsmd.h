@@ -593,13 +593,66 @@ int qsmd_check_pending_batch_device(qsmd_ctx* ctx, uint32_t model_id,
  * n_keys).  No keyed table set: QSMD_ERR_ARG.  QSMD_FLAG_EARLY_EXIT_BATCH:
  * QSMD_ERR_UNSUPPORTED.
  *
- * It is always the plain search on the product: the knobs "ktable_memo",
- * "ktable_local", "table_memo" and "pending_memo" do not reach it, and
- * "ktable_local_last" and "pending_memo_hits_last" are not moved by it
- * ("table_memo_hits_last" reads 0 after it, as after qsmd_check_pending_batch
- * without its memo).  One workgroup needs the component's tables and 12 / 24
- * / 48 KB of LDS (32 / 64 / 128-event class): 128 KB at the largest component
- * in the widest class. */
+ * By default it is the plain search on the product, and always the plain
+ * search: the knobs "ktable_memo", "ktable_local", "table_memo" and
+ * "pending_memo" do not reach it, and "ktable_local_last" and
+ * "pending_memo_hits_last" are not moved by it ("table_memo_hits_last" reads
+ * 0 after it, as after qsmd_check_pending_batch without its memo).  One
+ * workgroup needs the component's tables and 12 / 24 / 48 KB of LDS (32 / 64 /
+ * 128-event class): 128 KB at the largest component in the widest class.
+ *
+ * Local mode -- knob "kpending_local" (qsmd_set_param / qsmd_get_param;
+ * default 0 = off: every launch and result as above; 1 = on; any other value
+ * QSMD_ERR_ARG and the old value stays).  The rule above is local as well: a
+ * pending invocation on one key helps no other.  With the knob at 1,
+ * qsmd_check_kpending_batch and qsmd_check_kpending_batch_device check every
+ * history that is *splittable here* key by key.  The knob reaches no other
+ * call ("ktable_local" is the check call's and does not reach this one);
+ * "ktable_memo", "table_memo" and "pending_memo" still do not reach this call.
+ *   - Splittable here is QSMD_MODEL_KTABLE's definition (above) with one
+ *     change to (2): a pid's events in history order alternate invocation,
+ *     response, ..., from an invocation, and may end on an invocation.  That
+ *     last invocation is pending and belongs to the key in its own a byte.
+ *     Still on the product route, status and nodes those of the knob at 0 bit
+ *     for bit: a lone response (a pid whose first event, or whose event after
+ *     a response, is a response); a pid with two operations in flight, which
+ *     covers an invocation after a pending one of the same pid; every encode
+ *     error (a code >= n_inv / n_resp, a key >= n_keys); a header that fails
+ *     the header test (model_id != 5, n_ev > 128, ev_off + n_ev > n_events).
+ *   - Sub-history k, for each key k in ascending order: the events of the
+ *     operations invoked on key k (an operation is an invocation and, if the
+ *     pid has a later event, the pid's next event), in history order, bytes
+ *     unchanged, the same header but for ev_off and n_ev.  Each is searched
+ *     by the rule above with the call's flags, max_nodes (applied to each
+ *     part on its own), time limit, "table_budget" and model0's state for
+ *     that key (the whole model0 vector is passed on; a part moves one key's
+ *     state only).  Every part is searched: no short cut across keys.
+ *   - The rule's last sentence applies per part: a part with no response
+ *     event whose root has no child is LINEARISABLE with 0 nodes.  A key with
+ *     no operation is an empty part: LINEARISABLE, 0 nodes.
+ *   - The history's status is that of the lowest key whose part is not
+ *     LINEARISABLE, or LINEARISABLE when there is none; its nodes is the sum
+ *     over its parts.  qsmd_totals counts histories (nodes: the sum of the
+ *     per-history values); qsmd_timed_out and "table_pass2_last" describe the
+ *     launch over the parts.
+ *   - A call that carries QSMD_FLAG_WITNESS takes the product route whole,
+ *     witness and assumed included, as if the knob were 0, and
+ *     "kpending_local_last" reads 0 after it.  So does a call with more than
+ *     (2^32-1) / n_keys histories.
+ *   - "kpending_local_last" (qsmd_get_param; waits for the call): the
+ *     histories that were split in the most recent keyed pending call, 0 when
+ *     it took the product route.  The two counters are separate:
+ *     "ktable_local_last" is not moved by a keyed pending call,
+ *     "kpending_local_last" is not moved by a check call.
+ *   - The call stays asynchronous on the caller's stream.  As for
+ *     "ktable_local", with the knob at 1 the event slots [ev_off, ev_off +
+ *     n_ev) of different headers must not overlap.
+ * Promised: for a component without post_err, a splittable history's verdict
+ * is the product route's whenever neither side ends in BUDGET.  Not promised:
+ * node counts are per key, summed, not the product's; BUDGET is per key (a
+ * history the product search leaves BUDGET is usually decided); and with
+ * post_err a failing history may read NONLINEARISABLE where the product reads
+ * MODEL_ERROR, or the reverse.  The ABI version is unchanged. */
 
 /* Host memory, synchronous (as qsmd_check_batch). */
 int qsmd_check_kpending_batch(qsmd_ctx* ctx,

@@ -221,6 +221,10 @@ struct qsmd_ctx {
     bool ktable_local_call = false;    // the most recent model-5 call took the local route
     char* kl = nullptr;
     size_t kl_bytes = 0;
+    // the keyed pending call's local mode (knob "kpending_local"; 0 = off: the
+    // product search), in the same workspace; neither knob reaches the other's call
+    uint64_t kpending_local = 0;
+    bool kpending_local_call = false;  // the most recent keyed pending call took the local route
     uint8_t* wf_rank_host = nullptr;   // wellformed: pid rank table (pinned) and its device copy
     char* wf_rank_dev = nullptr;
     size_t wf_rank_bytes = 0;
@@ -573,7 +577,10 @@ int qsmd_set_param(qsmd_ctx* c, const char* name, uint64_t value) {
     } else if (n == "ktable_local") {       // QSMD_MODEL_KTABLE: each key searched on its own (csrc/ksplit.hip)
         if (value > 1) return fail(c, QSMD_ERR_ARG, "ktable_local: 0 (the product search) or 1");
         c->ktable_local = value;
-    } else if (n == "table_memo_grid") {    // diagnostic: pass 2's workgroups at most with the memo (0 = automatic)
+    } else if (n == "kpending_local") {     // the same for qsmd_check_kpending_batch, and for it only
+        if (value > 1) return fail(c, QSMD_ERR_ARG, "kpending_local: 0 (the product search) or 1");
+        c->kpending_local = value;
+    } else if (n == "table_memo_grid") {   // diagnostic: pass 2's workgroups at most with the memo (0 = automatic)
         if (value > 65536) return fail(c, QSMD_ERR_ARG, "table_memo_grid in 0..65536");
         c->table_memo_grid = value;
     } else if (n == "heavy_mode") {
@@ -893,8 +900,10 @@ static int check_table_locked(qsmd_ctx* c, const qsmd_hdr* hdr, uint64_t n_hist,
     // with the search kernels of csrc/tpending.hip, the memo under its own
     // knob ("pending_memo"; "table_memo" does not reach it) -- or a
     // qsmd_check_kpending_batch call (model 5) -- the keyed launches with the
-    // search kernels of csrc/kpending.hip, always the plain search on the
-    // product: no memo, no local mode, and neither mode's counters are moved
+    // search kernels of csrc/kpending.hip, always the plain search: no memo,
+    // and neither the check call's memo nor its local mode ("ktable_local")
+    // reach it or have their counters moved; its own local mode is the knob
+    // "kpending_local" (below)
     // explain != null: a qsmd_explain_batch call -- the same launches with the
     // EXPLAIN instantiations, always the plain search on the product (no
     // memo, no local mode, no witness: the path is the witness)
@@ -929,13 +938,20 @@ static int check_table_locked(qsmd_ctx* c, const qsmd_hdr* hdr, uint64_t n_hist,
     // narrower than it) into c->kl, and the combine kernels fold the parts'
     // results into the caller's outputs -- one stream, no host round trip.  A
     // call with a witness, or one whose sub-headers would pass 2^32-1, takes
-    // the product route whole.
+    // the product route whole.  A keyed pending call does the same under its
+    // own knob ("kpending_local"): the split kernel's pending form, the
+    // pending search over the sub-headers without `assumed`, the same combine
+    // with the split count in a probe slot of its own; each call's knob and
+    // counter are out of the other's reach.
     KSplitArgs ks{};
     bool local = false;
     if constexpr (KEYED) {
-        local = c->ktable_local != 0 && !explain && !pending && !(flags & QSMD_FLAG_WITNESS) &&
+        local = (pending ? c->kpending_local : c->ktable_local) != 0 && !explain && !(flags & QSMD_FLAG_WITNESS) &&
                 n_hist * (uint64_t)c->ktab_keys <= 0xFFFFFFFFull;
-        if (!pending) c->ktable_local_call = local;
+        if (pending)
+            c->kpending_local_call = local;
+        else
+            c->ktable_local_call = local;
         if (local) {
             const uint64_t n_sub = n_hist * c->ktab_keys;
             const size_t o_bk = 256;
@@ -964,8 +980,9 @@ static int check_table_locked(qsmd_ctx* c, const qsmd_hdr* hdr, uint64_t n_hist,
             ks.buckets = reinterpret_cast<unsigned long long*>(c->kl + o_bk);
             ks.n_split = reinterpret_cast<uint32_t*>(c->kl);
             ks.probe_host = c->probe_host;
+            ks.probe_slot = pending ? kProbeKPendLocal : kProbeKLocal;
             const uint32_t grid = (uint32_t)std::min<uint64_t>(std::max<uint64_t>(n_hist, 1), 32ull * c->n_cu);
-            HIP_TRY(c, launch_ksplit(ks, grid, s), "split launch");
+            HIP_TRY(c, launch_ksplit(ks, grid, s, pending), "split launch");
             // from here on the call is the search of the parts; its totals
             // stay in the workspace
             hdr = ks.sub_hdr;
@@ -2158,6 +2175,11 @@ int qsmd_get_param(qsmd_ctx* c, const char* name, uint64_t* out) {
     } else if (n == "ktable_local_last") {   // histories split in the most recent QSMD_MODEL_KTABLE call
         quiesce(c);
         *out = c->ktable_local_call ? c->probe_host[kProbeKLocal] : 0u;
+    } else if (n == "kpending_local") {
+        *out = c->kpending_local;
+    } else if (n == "kpending_local_last") {   // histories split in the most recent keyed pending call
+        quiesce(c);
+        *out = c->kpending_local_call ? c->probe_host[kProbeKPendLocal] : 0u;
     } else if (n == "table_memo_grid") {
         *out = c->table_memo_grid;
     } else if (n == "table_memo_hits_last") {   // memo hits of the most recent QSMD_MODEL_TABLE call

@@ -547,7 +547,12 @@ hipError_t launch_ktable_pending(const KTableArgs& p, const uint32_t grid1[3], c
 // the events grouped by key into the context's workspace, launch_table
 // searches the sub-headers as an ordinary model-5 batch into sub_status /
 // sub_nodes, and the combine kernels fold those into the caller's outputs.
+// The keyed pending call's local mode (knob "kpending_local") is the same
+// three steps with the split kernel's pending form (a pid's events may end on
+// an invocation, which belongs to its own key), launch_ktable_pending over the
+// sub-headers, and a probe slot of its own for the split count.
 constexpr int kProbeKLocal = 16;        // probe_host: histories split in the most recent local call
+constexpr int kProbeKPendLocal = 20;    // the same for the most recent keyed pending call
 constexpr int kProbeWords = 32;         // qsmd_ctx::probe_host, in 32-bit words
 struct KSplitArgs {
     const qsmd_hdr* hdr;          // the caller's
@@ -565,8 +570,10 @@ struct KSplitArgs {
     unsigned long long* buckets;  // [kBuckets][kBucketWords], zeroed per call
     uint32_t* n_split;            // device counter, zeroed per call
     uint32_t* probe_host;         // pinned
+    uint32_t probe_slot;          // where the split count goes: kProbeKLocal or kProbeKPendLocal
 };
-hipError_t launch_ksplit(const KSplitArgs& p, uint32_t grid, hipStream_t s);
+// pending: the split kernel's pending form (the keyed pending call)
+hipError_t launch_ksplit(const KSplitArgs& p, uint32_t grid, hipStream_t s, bool pending = false);
 // combine + totals and the split count (after launch_table on the same stream)
 hipError_t launch_kcombine(const KSplitArgs& p, hipStream_t s);
 

@@ -19,6 +19,11 @@
 //                   call's totals count histories.
 //   ksplit_finish   totals from the buckets, the split count for the host.
 //
+// The keyed pending call's local mode (knob "kpending_local")
+// is the same with ksplit_split_pending -- a pid's events may end on an
+// invocation -- and launch_ktable_pending over the sub-headers; the split
+// count then goes to a probe slot of its own (KSplitArgs::probe_slot).
+//
 // Splittable = encode-valid by the search's own test (ktable_bin's header test
 // and stage_ktable's per event: code < n_inv / n_resp, an invocation's key <
 // n_keys) and, per pid, events that alternate invocation, response, ...,
@@ -92,7 +97,14 @@ __device__ __forceinline__ void split_load(const KSplitArgs& a, const SplitHdr& 
 // The loop is pipelined over the workgroup's histories: while history i is
 // split, the events of i + 1 and the header of i + 2 are in flight, so a
 // wavefront pays neither load's latency per history.
-__global__ __launch_bounds__(C_LANES) void ksplit_split(KSplitArgs a) {
+//
+// PENDING (the keyed pending call, knob "kpending_local"): a pid's events may
+// end on an invocation -- the rank's parity must still match the event's kind,
+// the pid's count may be odd.  That last invocation takes its key from its own
+// `a` byte like every other one (validated < n_keys by the same test), so the
+// destinations are a permutation of the history's slot as before.
+template <bool PENDING>
+__device__ __forceinline__ void split_histories(const KSplitArgs& a) {
     __shared__ uint32_t lw[kMaxEv];              // the first word of every event
     __shared__ uint2 perm[kMaxEv];               // the events in sub-history order
     const uint32_t lane = threadIdx.x;
@@ -175,7 +187,8 @@ __global__ __launch_bounds__(C_LANES) void ksplit_split(KSplitArgs a) {
                 // stage_ktable's test
                 const bool valid = resp ? code < a.n_resp : (code < a.n_inv && ka < a.n_keys);
                 // the pid's events alternate from an invocation and end on a response
-                const bool paired = ((rank[r] & 1u) != 0u) == resp && (cnt[r] & 1u) == 0u;
+                // (PENDING: or on an invocation)
+                const bool paired = ((rank[r] & 1u) != 0u) == resp && (PENDING || (cnt[r] & 1u) == 0u);
                 bad = bad || (act[r] && !(valid && paired));
                 key[r] = (resp ? (prev >> 16) : ka) & 7u;
             }
@@ -223,6 +236,10 @@ __global__ __launch_bounds__(C_LANES) void ksplit_split(KSplitArgs a) {
     if (lane == 0u && n_split) atomicAdd(a.n_split, n_split);
 }
 
+__global__ __launch_bounds__(C_LANES) void ksplit_split(KSplitArgs a) { split_histories<false>(a); }
+
+__global__ __launch_bounds__(C_LANES) void ksplit_split_pending(KSplitArgs a) { split_histories<true>(a); }
+
 // One lane per history: the results of its n_keys sub-searches, folded.
 __global__ __launch_bounds__(C_LANES) void ksplit_combine(KSplitArgs a) {
     const int lane = threadIdx.x;
@@ -255,15 +272,18 @@ __global__ __launch_bounds__(C_LANES) void ksplit_finish(KSplitArgs a) {
         reinterpret_cast<uint64_t*>(a.totals)[k] = v;
     }
     if (k == 0 && a.probe_host) {
-        a.probe_host[kProbeKLocal] = *a.n_split;
+        a.probe_host[a.probe_slot] = *a.n_split;
         __threadfence_system();
     }
 }
 
 }  // namespace
 
-hipError_t launch_ksplit(const KSplitArgs& p, uint32_t grid, hipStream_t s) {
-    hipLaunchKernelGGL(ksplit_split, dim3(std::max(grid, 1u)), dim3(C_LANES), 0, s, p);
+hipError_t launch_ksplit(const KSplitArgs& p, uint32_t grid, hipStream_t s, bool pending) {
+    if (pending)
+        hipLaunchKernelGGL(ksplit_split_pending, dim3(std::max(grid, 1u)), dim3(C_LANES), 0, s, p);
+    else
+        hipLaunchKernelGGL(ksplit_split, dim3(std::max(grid, 1u)), dim3(C_LANES), 0, s, p);
     return hipGetLastError();
 }
 

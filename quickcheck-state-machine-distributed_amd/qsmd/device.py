@@ -409,6 +409,12 @@ class Context:
         the product; qsmd_get_param "ktable_local_last")."""
         return self.get_param("ktable_local_last")
 
+    def kpending_local_last(self):
+        """Histories that were split by key in the most recent
+        qsmd_check_kpending_batch call (knob "kpending_local"; 0 when the call
+        searched the product; qsmd_get_param "kpending_local_last")."""
+        return self.get_param("kpending_local_last")
+
     def table_memo_hits(self):
         """Hits of the second pass's state memo (knob "table_memo"; for a
         QSMD_MODEL_KTABLE call "ktable_memo") in the most recent table call

@@ -111,7 +111,7 @@ class CheckResult:
 
 def linearisable_batch(model, histories, model0=None, *, max_nodes=0, witness=False,
                        flags=device.QSMD_FLAG_EXHAUSTIVE, ctx=None, table_memo=None,
-                       ktable_local=None, pending=None, pending_memo=None) -> CheckResult:
+                       ktable_local=None, pending=None, pending_memo=None, kpending_local=None) -> CheckResult:
     """Check many histories in one device call.  ``table_memo`` (table models:
     entries per lane slot of the second pass's state memo, 0 = off) sets the
     context's "table_memo" knob for this call and restores it afterwards;
@@ -130,6 +130,12 @@ def linearisable_batch(model, histories, model0=None, *, max_nodes=0, witness=Fa
     responses that were assumed.  With raise tables this can read ``error``
     where None reads ``lin``; "table_memo" is ignored, and for a keyed model
     so are "ktable_memo" and "ktable_local" (the plain search on the product).
+    ``kpending_local`` (only with ``pending="complete"`` and a
+    :class:`KeyedTableModel`): None leaves the context's "kpending_local" knob
+    alone, True / False set it for this call and restore it afterwards --
+    every history that is splittable with pending invocations
+    (:meth:`KeyedTableModel.split_history` with ``pending=True``) is then
+    checked key by key; a call with ``witness`` searches the product whole.
     ``pending_memo`` (only with ``pending="complete"`` and a
     :class:`TableModel`: entries per lane slot, 0 = off) sets the pending
     call's own memo knob, "pending_memo", for this call and restores it
@@ -145,6 +151,8 @@ def linearisable_batch(model, histories, model0=None, *, max_nodes=0, witness=Fa
                                   '(QSMD_MODEL_TABLE, QSMD_MODEL_KTABLE)')
     if pending_memo is not None and keyed:
         raise ValueError("pending_memo: the keyed pending call has no memo")
+    if kpending_local is not None and not (pending and keyed):
+        raise ValueError('kpending_local: only with a KeyedTableModel and pending="complete"')
     batch = codec.encode(m, histories, model0)
     accounts0 = m.new_account_map(model0)
     packed = m.pack_model0(model0, accounts0)
@@ -170,6 +178,10 @@ def linearisable_batch(model, histories, model0=None, *, max_nodes=0, witness=Fa
     if pending_memo is not None:
         saved_pending = ctx.get_param("pending_memo")
         ctx.set_param("pending_memo", pending_memo)
+    saved_klocal = None
+    if kpending_local is not None:
+        saved_klocal = ctx.get_param("kpending_local")
+        ctx.set_param("kpending_local", 1 if kpending_local else 0)
     assumed = None
     try:
         if pending and keyed:
@@ -188,16 +200,20 @@ def linearisable_batch(model, histories, model0=None, *, max_nodes=0, witness=Fa
             ctx.set_param("ktable_local", saved_local)
         if saved_pending is not None:
             ctx.set_param("pending_memo", saved_pending)
+        if saved_klocal is not None:
+            ctx.set_param("kpending_local", saved_klocal)
     return CheckResult(batch, status, nodes, wit, totals, assumed=assumed)
 
 
 def linearisable(transition, postcondition, model0, history, *, max_nodes=0, ctx=None, table_memo=None,
-                 ktable_local=None, pending=None, pending_memo=None) -> bool:
+                 ktable_local=None, pending=None, pending_memo=None, kpending_local=None) -> bool:
     """``linearisable`` (src/Linearisability.hs:52-69) on the GPU
-    (``table_memo``, ``ktable_local``, ``pending``, ``pending_memo``: see :func:`linearisable_batch`)."""
+    (``table_memo``, ``ktable_local``, ``pending``, ``pending_memo``, ``kpending_local``: see
+    :func:`linearisable_batch`)."""
     m = _device_model(transition, postcondition)
     res = linearisable_batch(m, [history], model0, max_nodes=max_nodes, ctx=ctx, table_memo=table_memo,
-                             ktable_local=ktable_local, pending=pending, pending_memo=pending_memo)
+                             ktable_local=ktable_local, pending=pending, pending_memo=pending_memo,
+                             kpending_local=kpending_local)
     st = int(res.status[0])
     if st == codec.STATUS_LIN:
         return True

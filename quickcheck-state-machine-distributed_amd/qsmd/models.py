@@ -646,11 +646,14 @@ class KeyedTableModel(DeviceModel):
             return None
         return (ctypes.c_uint32 * self.n_keys)(*[self.component._state(s) for s in self._model(model0)])
 
-    def split_history(self, history):
+    def split_history(self, history, pending=False):
         """The per-key sub-histories the local mode searches (knob
         "ktable_local", include/qsmd.h): ``None`` when ``history`` is not
         *splittable*, else ``[(key, sub_history), ...]`` in ascending key
-        order, keys with no operation left out.
+        order, keys with no operation left out.  ``pending=True`` is the
+        split of the keyed pending call's local mode (knob "kpending_local"):
+        a pid's events may end on an invocation, which is pending and belongs
+        to its own key; everything else is refused as below.
 
         Splittable: at most 128 events, every invocation a ``(key, inv)`` of
         this model and every response one of the component's, and every pid's
@@ -681,7 +684,7 @@ class KeyedTableModel(DeviceModel):
                     return None
                 k = open_key.pop(pid)
             parts.setdefault(k, []).append((pid, (kind, x)))
-        if open_key:
+        if open_key and not pending:
             return None
         return sorted(parts.items())
 

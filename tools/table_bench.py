@@ -62,11 +62,17 @@ DESIGN.md §10j) at that size and carry "pending_memo" and "pending_memo_hits". 
 register batch of the default run, or with --keyed K the keyed batch above as
 QSMD_MODEL_KTABLE alone (no flat product): the keyed check call against
 qsmd_check_kpending_batch_device (csrc/kpending.hip), which has
-no memo and no local mode -- --memo sizes the check lines only, --local stays 0.
+no memo -- --memo sizes the check lines only.  --keyed K --pending --local adds
+the keyed pending call's own local mode (knob "kpending_local", DESIGN.md §10l:
+every history splittable with pending invocations checked key by key) on the
+complete and on the crashed batch, five calls interleaved; a pending line
+carries "kpending_local" and "kpending_local_last", and "ktable_local" stays 0.
+With --pending, --clients C --ops K shape the host generator's batch (3 % per
+operation as before).
 
     python tools/table_bench.py [--budgets default,0] [--memo 0,64,256,1024,4096] [--distinct 65536] [--n 1048576]
                                 [--wide 0|1|both] [--model register|kv] [--generated] [--seed S] [--keyed K]
-                                [--local 0,1] [--clients C] [--ops K] [--p-bug P] [--explain] [--pending]
+                                [--local [0,1]] [--clients C] [--ops K] [--p-bug P] [--explain] [--pending]
 """
 
 import argparse
@@ -102,7 +108,7 @@ def main():
     ap.add_argument("--generated", action="store_true")
     ap.add_argument("--seed", type=int, default=0x7AB1E)
     ap.add_argument("--keyed", type=int, default=0)
-    ap.add_argument("--local", default="0")
+    ap.add_argument("--local", nargs="?", const="1", default="0")
     ap.add_argument("--clients", type=int, default=4)
     ap.add_argument("--ops", type=int, default=16)
     ap.add_argument("--p-bug", type=float, default=0.39)
@@ -111,12 +117,16 @@ def main():
     args = ap.parse_args()
     if args.pending and (args.generated or args.wide != "0" or args.model != "register" or args.explain):
         ap.error("--pending runs the register batch of the default run (or of --keyed K) alone")
-    if args.pending and args.keyed and args.local != "0":
-        ap.error("--pending: the keyed pending call has no local mode")
+    if args.pending and args.keyed and args.local not in ("0", "1"):
+        ap.error("--pending --local: the keyed pending call's local mode beside the product route (no value)")
     if args.local != "0" and not args.keyed:
         ap.error("--local is the keyed path's (--keyed K)")
-    if (args.clients, args.ops, args.p_bug) != (4, 16, 0.39) and not args.generated:
-        ap.error("--clients / --ops / --p-bug shape the --generated batch")
+    if ((args.clients, args.ops) != (4, 16) and not (args.generated or args.pending)) or \
+            (args.p_bug != 0.39 and not args.generated):
+        ap.error("--clients / --ops shape the --generated or the --pending batch, --p-bug the --generated one")
+    kpending_local = args.pending and args.keyed and args.local == "1"
+    if args.pending:
+        args.local = "0"                    # (the check lines stay on the product)
     if args.keyed and (args.wide != "0" or args.model != "register"):
         ap.error("--keyed runs the register model alone")
     tiled = args.distinct is not None or not args.generated
@@ -189,7 +199,7 @@ def main():
                 (f"{args.distinct} distinct tiled to {n}" if reps > 1 else f"{n} distinct"))
     else:
         rng = random.Random("table_bench")
-        hists = [tg.gen_history(model, rng, 4, 16, 0.03) for _ in range(args.distinct)]
+        hists = [tg.gen_history(model, rng, args.clients, args.ops, 0.03) for _ in range(args.distinct)]
         def encoded(mid, hs):               # the histories in a model's encoding
             if args.keyed == 1 and mid == 5:        # the one key
                 hs = [[(p, (k, (0, x) if k == "L" else x)) for p, (k, x) in h] for h in hs]
@@ -220,7 +230,8 @@ def main():
             d_hdr_c = torch.from_numpy(hdr.view(np.uint8).copy()).to(dev)
             d_ev_c = torch.from_numpy(np.tile(batch.events, reps).view(np.uint8)).to(dev)
             n_events_c = per_c * reps
-        what = f"{model['name']} 4x16 p_bug 0.03, {args.distinct} distinct tiled to {n}, device-resident"
+        what = (f"{model['name']} {args.clients}x{args.ops} p_bug 0.03, {args.distinct} distinct tiled to {n}, "
+                "device-resident")
     d_st = torch.empty(n, dtype=torch.uint8, device=dev)
     d_nd = torch.empty(n, dtype=torch.int64, device=dev)
     d_tot = torch.zeros(8, dtype=torch.int64, device=dev)
@@ -231,7 +242,9 @@ def main():
     cross = [(b, int(e), mid, int(loc), call) for _ in range(args.rounds) for b in args.budgets.split(",")
              for e in args.memo.split(",") for mid in ids for loc in (args.local.split(",") if mid == 5 else "0")
              for call in (("check", "explain") if args.explain else
-                          ("check", "pending", "pending/crash") if args.pending else ("check",))]
+                          ("check", "pending", "pending/crash") +
+                          (("pending+local", "pending/crash+local") if kpending_local else ())
+                          if args.pending else ("check",))]
     for b, entries, mid, local, call in cross:
         d_hdr, d_ev = d_hdrs[mid], d_evs.get(mid, next(iter(d_evs.values())))
         budget = default if b == "default" else int(b)
@@ -242,6 +255,10 @@ def main():
         ctx.set_param("ktable_local", local)
         # (the pending call's memo is its own knob too: "table_memo" does not reach it)
         ctx.set_param("pending_memo", entries if call.startswith("pending") and mid != 5 else 0)
+        klocal = call.endswith("+local")    # the keyed pending call's own local mode
+        call = call.split("+")[0]
+        if kpending_local:
+            ctx.set_param("kpending_local", int(klocal))
         ms = []
         for k in range(args.warmup + args.calls):
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -277,6 +294,8 @@ def main():
             **({"pending_memo": entries, "pending_memo_hits": ctx.pending_memo_hits()}
                if call.startswith("pending") and mid != 5 else {}),
             "ktable_local": local, "ktable_local_last": ctx.ktable_local_last() if mid == 5 else 0,
+            **({"kpending_local": int(klocal), "kpending_local_last": ctx.kpending_local_last()}
+               if kpending_local and call.startswith("pending") else {}),
             "ms_per_call_median": round(med, 4), "ms_min": round(min(ms), 4), "ms_max": round(max(ms), 4),
             "histories_per_s": round(n / med * 1e3), "nodes_per_s": round(int(tot[7]) / med * 1e3),
             "nodes_per_call": int(tot[7]), "pass2_histories": ctx.table_pass2(),
