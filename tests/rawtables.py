@@ -1,5 +1,6 @@
 """Random raw tables whose responses move the state: the inputs of
-test_rawtables_host.py and test_gpu_rawtables.py.
+test_rawtables_host.py, test_gpu_rawtables.py and
+test_gpu_rawtables_kpending_local.py.
 
 TEST INFRASTRUCTURE ONLY.
 
@@ -23,6 +24,9 @@ and seeds are frozen: they were chosen so that the conditions
 test_rawtables_host.py asserts on the reference alone hold (every status
 reached, deep searches where a memo or pass 2 needs them, and (status, nodes)
 changing on most histories once ``on_resp`` is replaced by identity rows).
+:data:`KEYED_LOCAL` and the helpers at the end of the file are the inputs of
+the keyed pending call's local mode
+(tests/test_gpu_rawtables_kpending_local.py).
 """
 
 from __future__ import annotations
@@ -35,6 +39,7 @@ import numpy as np
 
 import anyshape as an
 import explain_ref as xr
+import kpendinglocal_ref as klr
 import ktablegen as kg
 import pending_ref as pr
 import tablegen as tg
@@ -79,6 +84,36 @@ KEYED = {
     "k_one": ("n_r32", 1, None),
 }
 DEEP = ("n_deep", "n_1inv", "k_deep")       # at least one budget, ten searches beyond pass 1's 256 nodes
+# The shapes of the keyed pending call's local mode (knob "kpending_local"), apart from KEYED so that the
+# parametrisations over KEYED do not grow: two-key products whose *parts* pass pass 1's 256 nodes and reach a
+# low max_nodes, and eight-key products for keyed_walk.  k8_r2's model0 holds every state of n_r2.
+KEYED_LOCAL = {
+    "k2_deep": ("n_deep", 2, None),
+    "k2_r32": ("n_r32", 2, None),
+    "k8_1inv": ("n_1inv", 8, None),
+    "k8_r2": ("n_r2", 8, (0, 3, 1, 4, 2, 0, 4, 1)),
+}
+LOCAL_SHAPES = ("k_max", "k_deep", "k_odd", "k2_deep", "k2_r32")    # every history of their crashed batches splits
+LOW_NODES = 40                              # the low max_nodes at which parts of k2_deep / k2_r32 are `budget`
+# The crash draws of the KEYED_LOCAL ids carry this suffix in their seed string.  Without it 2 of k2_deep's and 1
+# of k2_r32's 410 crashed histories are `error` on the product and `lin` key by key (ERROR_LIN_KAT is one of
+# them), which happened at 5 of 12 suffixes tried on k2_deep and at 5 of 12 on k2_r32; "/3" is the first at which
+# neither shape has such a history, so that test_rawtables_host.py can assert on whole batches that the product
+# and the local mode disagree in two ways only.  The choice looked at the two restatements alone.
+LOCAL_CRASH_SALT = "/3"
+# k2_r32: `error` after 20 nodes on the product, `lin` key by key (key 0: 9 nodes, key 1: 11).  The product
+# search, after a failure on key 0, backtracks into other orders of key 1's operations and meets an entry of
+# post_err there; key 1's own search is linearisable on its first order and never visits it.
+ERROR_LIN_KAT = [
+    (0, ("L", (1, 2))), (0, ("R", 28)), (0, ("L", (0, 1))), (3, ("L", (0, 2))), (1, ("L", (0, 0))), (3, ("R", 0)),
+    (1, ("R", 27)), (3, ("L", (0, 1))), (0, ("R", 12)), (2, ("L", (0, 1))), (2, ("R", 19)), (0, ("L", (0, 0))),
+    (2, ("L", (1, 1))), (1, ("L", (0, 2))), (3, ("R", 8)), (3, ("L", (0, 1))), (3, ("R", 29)), (0, ("R", 11)),
+    (3, ("L", (1, 1))), (0, ("L", (0, 2))), (0, ("R", 2)), (3, ("R", 30))]
+
+
+def keyed_spec(name):
+    """(component, keys, model0) of an id of KEYED or KEYED_LOCAL, else None."""
+    return KEYED.get(name) or KEYED_LOCAL.get(name)
 
 
 def tables(seed, ns, ni, nr, p_post, p_err, high_bits):
@@ -128,8 +163,8 @@ def closures(name, identity_resp=False, ignore_err=False):
     ``identity_resp`` / ``ignore_err``: the variants that show the inputs
     depend on ``on_resp`` / ``post_err`` (a response leaves the state alone /
     nothing raises); the generated system (``real``) stays the true one."""
-    if name in KEYED:
-        comp, K, model0 = KEYED[name]
+    if keyed_spec(name):
+        comp, K, model0 = keyed_spec(name)
         p = kg.product(closures(comp, identity_resp, ignore_err), K)
         p["name"] = name
         if model0 is not None:
@@ -168,8 +203,8 @@ def model(name, wide=None):
     through the explicit constructor: a TableModel, a WideTableModel (the
     WIDE shapes and the TWINS) or a KeyedTableModel."""
     from qsmd.models import KeyedTableModel, TableModel, WideTableModel
-    if name in KEYED:
-        comp, K, _ = KEYED[name]
+    if keyed_spec(name):
+        comp, K, _ = keyed_spec(name)
         return KeyedTableModel(model(comp), K)
     sp, t = spec(name), tables_of(name)
     wide = (name in WIDE or name in TWINS) if wide is None else wide
@@ -181,7 +216,7 @@ def model(name, wide=None):
 
 def model0_of(name):
     """The model0 a keyed shape is generated and checked from (None: init_model)."""
-    return KEYED[name][2] if name in KEYED else None
+    return keyed_spec(name)[2] if keyed_spec(name) else None
 
 
 # ---------------------------------------------------------------------------
@@ -211,10 +246,17 @@ def variant_ref(name, setting, variant):
 
 
 @functools.lru_cache(maxsize=None)
+def crashed(name, setting):
+    """The check batch with clients crashed."""
+    salt = LOCAL_CRASH_SALT if name in KEYED_LOCAL else ""
+    rng = random.Random(f"rawtables/crash/{name}/{setting}{salt}")
+    return [pr.crash(h, rng, CRASH) for h in histories(name, setting)]
+
+
+@functools.lru_cache(maxsize=None)
 def crash_case(name, setting):
     """The check batch with clients crashed, and pending_ref's results."""
-    rng = random.Random(f"rawtables/crash/{name}/{setting}")
-    hists = [pr.crash(h, rng, CRASH) for h in histories(name, setting)]
+    hists = crashed(name, setting)
     c = closures(name)
     return hists, [pr.linearisable_pending(c, h, MAX_NODES) for h in hists]
 
@@ -265,3 +307,135 @@ def pending_walk(name, n, start=None, first_pid=0):
         s = int(t.on_resp[t.on_inv[s, i], (a & -a).bit_length() - 1])
         states.append(s)
     return h, states
+
+
+# ---------------------------------------------------------------------------
+# the keyed pending call's local mode (tests/kpendinglocal_ref.py)
+# ---------------------------------------------------------------------------
+
+def inits_of(name):
+    """The per-key start states of a keyed id."""
+    comp, K, model0 = keyed_spec(name)
+    return (spec(comp).init,) * K if model0 is None else tuple(model0)
+
+
+def local_parts(name, hist, max_nodes, c=None):
+    """The restatement on one history, part by part: None when it does not
+    split, else ([(key, status, nodes)], [path]) in ascending key order, every
+    part searched with the component's closures ``c`` from its key's model0
+    state."""
+    comp, K, _ = keyed_spec(name)
+    c = closures(comp) if c is None else c
+    split = klr.split(c, K, hist)
+    if split is None:
+        return None
+    init = inits_of(name)
+    found = [(k, pr.linearisable_pending(c, klr.unkeyed(sub), max_nodes, init[k])) for k, sub in split]
+    return [(k, st, nd) for k, (st, nd, _) in found], [path for _, (_, _, path) in found]
+
+
+@functools.lru_cache(maxsize=None)
+def local_crash_case(name, setting, max_nodes=MAX_NODES, variant=None):
+    """The crashed batch of :func:`crash_case` under the local mode's
+    restatement: (histories, per history [(key, status, nodes)] of its parts
+    -- None for a history that does not split --, per history the combined
+    (status, nodes), per history the parts' paths).  ``variant``: the
+    "identity_resp" / "ignore_err" closures."""
+    comp = keyed_spec(name)[0]
+    c = closures(comp, **({variant: True} if variant else {}))
+    hists = crashed(name, setting)
+    found = [local_parts(name, h, max_nodes, c) for h in hists]
+    parts = [None if f is None else f[0] for f in found]
+    combined = [None if p is None else klr.combine([(st, nd) for _, st, nd in p]) for p in parts]
+    return hists, parts, combined, [None if f is None else f[1] for f in found]
+
+
+def keyed_walk(name, per_key):
+    """A keyed history of pending invocations only: every key gets
+    :func:`pending_walk`'s walk of ``per_key`` invocations on the component
+    from that key's model0 state, on pids of its own (key k: pids k * per_key
+    ...), the invocations rewritten to ``(k, i)``, the keys interleaved
+    round-robin.  Returns (history, the per-key end states)."""
+    comp, K, _ = keyed_spec(name)
+    walks, ends = [], []
+    for k, s in enumerate(inits_of(name)):
+        h, states = pending_walk(comp, per_key, start=s, first_pid=k * per_key)
+        walks.append([(pid, tg.L((k, i))) for pid, (_, i) in h])
+        ends.append(states[-1])
+    return [walks[k][d] for d in range(per_key) for k in range(K)], ends
+
+
+def empty_allowed(name):
+    """The (s, i) of a component at which no response is allowed although the
+    packed ``post`` word is not zero: its only bits are at or above ``n_resp``
+    or ones that ``post_err`` removes."""
+    sp, t = spec(name), tables_of(name)
+    return [(s, i) for s in range(sp.ns) for i in range(sp.ni)
+            if allowed_bits(name, s, i) == 0 and int(t.post_words[s, i]) != 0]
+
+
+WALK_PER_KEY = 16                           # 8 keys x 16 pending invocations: the 128 events of the widest class
+SHORT_WALK = 3
+
+
+def failing_walk(name, per_key=SHORT_WALK):
+    """:func:`keyed_walk` with ``per_key`` invocations per key and, on the
+    highest key, one completed operation of a pid of its own at the end: the
+    first (invocation, response) in table order that the walk's end state on
+    that key neither allows nor raises on and with which the restatement finds
+    the key's part `nonlin`.  Returns (history, the key, (inv, resp))."""
+    comp, K, _ = keyed_spec(name)
+    sp, t, c = spec(comp), tables_of(comp), closures(comp)
+    walk, ends = keyed_walk(name, per_key)
+    k, end = K - 1, ends[K - 1]
+    for i in range(sp.ni):
+        for r in range(sp.nr):
+            if (allowed_bits(comp, end, i) >> r) & 1 or t.err[end, i, r]:
+                continue
+            h = walk + [(K * per_key, tg.L((k, i))), (K * per_key, tg.R(r))]
+            if dict((key, st) for key, st, _ in local_parts(name, h, MAX_NODES, c)[0])[k] == "nonlin":
+                return h, k, (i, r)
+    raise AssertionError(name)
+
+
+def empty_allowed_histories(name):
+    """For every (s, i) of :func:`empty_allowed` on the component whose state
+    ``s`` is some key's model0 state (the first such key, k), three histories:
+    the pending invocation ``(k, i)`` alone; with a complete, allowed
+    operation on the next key; with a complete operation on key k itself that
+    ``s`` allows.  [(s, i, k, [h1, h2, h3])]."""
+    comp, K, _ = keyed_spec(name)
+    sp, init = spec(comp), inits_of(name)
+
+    def allowed_op(s):
+        j = next(j for j in range(sp.ni) if allowed_bits(comp, s, j))
+        a = allowed_bits(comp, s, j)
+        return j, (a & -a).bit_length() - 1
+
+    out = []
+    for s, i in empty_allowed(comp):
+        if s not in init:
+            continue
+        k = init.index(s)
+        k2 = (k + 1) % K
+        alone = [(0, tg.L((k, i)))]
+        j2, r2 = allowed_op(init[k2])
+        j, r = allowed_op(s)
+        out.append((s, i, k, [alone, alone + [(1, tg.L((k2, j2))), (1, tg.R(r2))],
+                              alone + [(1, tg.L((k, j))), (1, tg.R(r))]]))
+    return out
+
+
+@functools.lru_cache(maxsize=None)
+def walk_case(name):
+    """The walk batch of a KEYED_LOCAL id: the 128-event walk, the short walk
+    with one failing key, the :func:`empty_allowed_histories`; with the local
+    restatement's parts and combined results and the product's
+    (pending_ref on the product closures)."""
+    hists = [keyed_walk(name, WALK_PER_KEY)[0], failing_walk(name)[0]]
+    for _, _, _, three in empty_allowed_histories(name):
+        hists += three
+    parts = [local_parts(name, h, MAX_NODES)[0] for h in hists]
+    combined = [klr.combine([(st, nd) for _, st, nd in p]) for p in parts]
+    c = closures(name)
+    return hists, parts, combined, [pr.linearisable_pending(c, h, MAX_NODES) for h in hists]

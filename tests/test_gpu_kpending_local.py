@@ -21,7 +21,7 @@ import pending_ref as pr
 import tablegen as tg
 from qsmd import codec, device
 from qsmd.linearisability import linearisable, linearisable_batch
-from qsmd.models import ModelError
+from qsmd.models import KeyedTableModel, ModelError
 from test_gpu_ktable import COMPONENTS, component, keyed, prod
 from test_gpu_table_pending import budget_knob
 from test_kpending_local_host import KAT_RULE2, KATS, Rd, Val, W
@@ -46,8 +46,15 @@ def ctx():
     c.close()
 
 
+def model_of(name, K):
+    """The keyed model of a COMPONENTS name and K; a KeyedTableModel given as
+    ``name`` is itself (K is then not looked at: the raw-table modules pass
+    their own models, and the restatement's closures as ``closures=``)."""
+    return name if isinstance(name, KeyedTableModel) else keyed(name, K)
+
+
 def encode(name, K, hists, model0=None):
-    batch = codec.encode(keyed(name, K), [list(h) for h in hists], model0)
+    batch = codec.encode(model_of(name, K), [list(h) for h in hists], model0)
     assert not batch.encode_errors
     return batch.hdr, batch.events
 
@@ -69,7 +76,7 @@ class knobs:
 
 
 def set_table(ctx, name, K):
-    m = keyed(name, K)
+    m = model_of(name, K)
     if ctx.keyed_table is not m:
         ctx.set_keyed_table(m)
     return m
@@ -123,12 +130,12 @@ def run_device(ctx, name, K, hdr, ev, local, **kw):
     return call.read() + (ctx.kpending_local_last(),)
 
 
-def expected(ctx, name, K, hdr, ev, max_nodes=MAXN, model0=None):
+def expected(ctx, name, K, hdr, ev, max_nodes=MAXN, model0=None, closures=None):
     """[(status code, nodes)] per header and the number of split histories:
     the restatement's result, and for a history it does not split the knob-0
     call's (at the default `table_budget`: the product route's results do not
-    depend on it)."""
-    want = klr.check_arrays(COMPONENTS[name], K, hdr, ev, max_nodes, model0)
+    depend on it).  ``closures``: the component's, when ``name`` is a model."""
+    want = klr.check_arrays(closures or COMPONENTS[name], model_of(name, K).n_keys, hdr, ev, max_nodes, model0)
     n_split = sum(w is not None for w in want)
     if n_split < len(want):
         st0, nd0, _, _, _, split0 = run_host(ctx, name, K, hdr, ev, 0, max_nodes, model0)
@@ -147,10 +154,10 @@ def assert_equal(want, n_split, st, nd, tot, split, max_nodes=MAXN):
     assert split == n_split
 
 
-def check_local(ctx, name, K, hdr, ev, max_nodes=MAXN, model0=None, budgets=BUDGETS, want=None):
+def check_local(ctx, name, K, hdr, ev, max_nodes=MAXN, model0=None, budgets=BUDGETS, want=None, closures=None):
     """Knob 1 through the host and the device entry, at every budget, against
     the expectation."""
-    want, n_split = want or expected(ctx, name, K, hdr, ev, max_nodes, model0)
+    want, n_split = want or expected(ctx, name, K, hdr, ev, max_nodes, model0, closures)
     for budget in budgets:
         with budget_knob(ctx, budget):
             st, nd, w, asm, tot, split = run_host(ctx, name, K, hdr, ev, 1, max_nodes, model0)

@@ -7,13 +7,21 @@
    replacing ``on_resp`` by identity rows changes (status, nodes) on at least
    half of the histories: these inputs see the fourth table.
 2. The Python mirror (qsmd.models.TableModel / WideTableModel /
-   KeyedTableModel, replay_witness, split_history) against the raw arrays."""
+   KeyedTableModel, replay_witness, split_history) against the raw arrays.
+3. The same for the keyed pending call's local mode (knob "kpending_local",
+   tests/kpendinglocal_ref.py): the conditions on the restatement that keep
+   tests/test_gpu_rawtables_kpending_local.py from passing vacuously, the
+   local verdicts against the product's, and split_history(pending=True)."""
+
+import collections
 
 import random
 
 import numpy as np
 import pytest
 
+import anyshape as an
+import kpendinglocal_ref as klr
 import ktablelocal_ref as kref
 import pending_ref as pr
 import rawtables as rt
@@ -28,7 +36,7 @@ PENDING = [n for n in SHAPES if n not in rt.WIDE]   # the shapes with a pending 
 
 
 def has_err(name):
-    return rt.spec(rt.KEYED[name][0] if name in rt.KEYED else name).p_err is not None
+    return rt.spec(rt.keyed_spec(name)[0] if rt.keyed_spec(name) else name).p_err is not None
 
 
 def union(name):
@@ -302,3 +310,253 @@ def test_split_history_is_the_restatements_split(name):
         assert m.split_history(h) == want
         split += want is not None
     assert rt.BATCHES["4x16"] <= split < len(hists)
+
+
+# ------------------------------------- 3. the keyed pending call's local mode on raw tables
+
+LOCAL = list(rt.LOCAL_SHAPES)
+TWO_KEYS = ["k2_deep", "k2_r32"]
+WALKS = ["k8_1inv", "k8_r2"]
+ALL_KEYED = list(rt.KEYED) + list(rt.KEYED_LOCAL)
+# what the restatement counts on the frozen batches, over all settings (DESIGN.md §10l records them; the GPU
+# module prints its pass-2 counts beside the first): parts beyond pass 1's 256 nodes at MAX_NODES; at LOW_NODES
+# the histories a `budget` part decides, those where one lies behind a lower failing key, those whose summed
+# nodes pass LOW_NODES; the product's `budget` histories the local mode decides at MAX_NODES
+PARTS_BEYOND_256 = {"k2_deep": 1, "k2_r32": 5}
+LOW = {"k2_deep": (18, 1, 24), "k2_r32": (27, 5, 45)}
+PRODUCT_BUDGET_DECIDED = {"k_max": 30, "k_deep": 13, "k_odd": 11, "k2_deep": 2, "k2_r32": 9}
+
+
+def test_the_local_shapes_are_apart_from_the_keyed_ones():
+    assert not set(rt.KEYED) & set(rt.KEYED_LOCAL) and not set(rt.KEYED_LOCAL) & set(SHAPES)
+    assert set(rt.LOCAL_SHAPES) <= set(ALL_KEYED) and set(TWO_KEYS + WALKS) == set(rt.KEYED_LOCAL)
+    for name, (comp, K, model0) in rt.KEYED_LOCAL.items():
+        m, c = rt.model(name), rt.closures(name)
+        assert isinstance(m, KeyedTableModel) and m.n_keys == K and m.component is rt.model(comp)
+        assert rt.model0_of(name) == model0 and c["name"] == name
+        assert c["init"] == rt.inits_of(name) == (model0 or (rt.spec(comp).init,) * K)
+    # k8_r2 starts every state of n_r2 somewhere, and not every key at 0
+    assert set(rt.inits_of("k8_r2")) == set(range(rt.spec("n_r2").ns)) and len(rt.inits_of("k8_r2")) == 8
+    assert rt.inits_of("k_max") == (255, 0, 17, 255, 128, 3, 254, 1)
+    assert 0 < rt.LOW_NODES < 256 < rt.MAX_NODES
+
+
+def part_state(comp, s, inv, r):
+    t = rt.tables_of(comp)
+    return int(t.on_resp[t.on_inv[s, inv], r])
+
+
+@pytest.mark.parametrize("name", LOCAL)
+def test_local_crashed_batches_have_teeth(name):
+    comp, K, model0 = rt.keyed_spec(name)
+    c, init = rt.closures(comp), rt.inits_of(name)
+    changed = changed_err = total = assumed_parts = invocations_only = 0
+    symbols, nexts = set(), set()
+    for setting, n in rt.BATCHES.items():
+        hists, parts, combined, paths = rt.local_crash_case(name, setting)
+        assert len(hists) == n and all(p is not None for p in parts)          # every history is splittable
+        assert combined == [klr.check(c, K, h, rt.MAX_NODES, model0) for h in hists]
+        assert sum(1 for h in hists if pr.pending_invocations(h)) > n // 3
+        if not (name in TWO_KEYS and setting == "3x10"):
+            assert sum(1 for p in parts if len(p) > 1) > n // 2
+        subs = [sub for h in hists for _, sub in klr.split(c, K, h)]
+        # (k_odd's frozen 6x24 batch -- 3 keys, 24 operations -- has no such part: the condition is the shape's)
+        invocations_only += sum(1 for sub in subs if all(e[1][0] == "L" for e in sub))
+        ident = rt.local_crash_case(name, setting, rt.MAX_NODES, "identity_resp")[2]
+        changed += sum(1 for a, b in zip(combined, ident) if a != b)
+        plain = rt.local_crash_case(name, setting, rt.MAX_NODES, "ignore_err")[2]
+        changed_err += sum(1 for a, b in zip(combined, plain) if a != b)
+        total += n
+        # parts that are linearisable only through an assumed response
+        for p, pa in zip(parts, paths):
+            for (k, st, _), path in zip(p, pa):
+                if st != "lin" or not any(op[3] for op in path):
+                    continue
+                assumed_parts += 1
+                s = init[k]
+                for _, inv, r, assumed in path:
+                    nxt = part_state(comp, s, inv, r)
+                    if assumed:
+                        symbols.add(r)
+                        nexts.add(nxt)
+                    s = nxt
+    print(name, "changed by identity_resp:", changed, "by ignore_err:", changed_err, "of", total,
+          "parts with an assumed response:", assumed_parts, "parts of invocations only:", invocations_only)
+    assert invocations_only >= 1
+    assert 2 * changed >= total
+    assert has_err(name) and changed_err >= 1
+    assert assumed_parts >= 10 and len(symbols) >= 2 and len(nexts) >= 2
+
+
+@pytest.mark.parametrize("name", LOCAL)
+def test_local_verdicts_against_the_products(name):
+    """Locality on raw tables: `lin` is `lin` on both sides wherever the
+    product decides, and a disagreement is the product's `budget` or a swap
+    within {error, nonlin}; the local mode decides some of those `budget`."""
+    pairs = collections.Counter()
+    for setting in rt.BATCHES:
+        hists, ref = rt.crash_case(name, setting)
+        hists2, _, combined, _ = rt.local_crash_case(name, setting)
+        assert hists2 is hists
+        pairs.update((r[0], c[0]) for r, c in zip(ref, combined))
+    print(name, "(product, per key):", dict(pairs))
+    for (whole, local), n in pairs.items():
+        if whole != "budget":
+            assert (whole == "lin") == (local == "lin"), (whole, local, n)
+        assert whole == local or whole == "budget" or {whole, local} == {"error", "nonlin"}, (whole, local, n)
+    decided = sum(n for (whole, local), n in pairs.items() if whole == "budget" and local != "budget")
+    assert decided >= 1 and decided == PRODUCT_BUDGET_DECIDED[name]
+
+
+def test_a_product_error_that_is_lin_key_by_key():
+    """The third kind of disagreement, which the frozen batches do not hold
+    (rawtables.LOCAL_CRASH_SALT): the product search raises where no key's own
+    search does."""
+    h = rt.ERROR_LIN_KAT
+    assert pr.linearisable_pending(rt.closures("k2_r32"), h, rt.MAX_NODES)[:2] == ("error", 20)
+    assert rt.local_parts("k2_r32", h, rt.MAX_NODES)[0] == [(0, "lin", 9), (1, "lin", 11)]
+    assert klr.check(rt.closures("n_r32"), 2, h, rt.MAX_NODES) == ("lin", 20)
+    # without post_err both are `lin`: the raise is all that differs
+    c = rt.closures("k2_r32", ignore_err=True)
+    assert pr.linearisable_pending(c, h, rt.MAX_NODES)[0] == "lin"
+
+
+@pytest.mark.parametrize("name", TWO_KEYS)
+def test_two_key_parts_pass_pass_1_and_reach_a_low_max_nodes(name):
+    beyond = sum(1 for s in rt.BATCHES for p in rt.local_crash_case(name, s)[1] for _, _, nd in p if nd > 256)
+    print(name, "parts beyond 256 nodes at", rt.MAX_NODES, ":", beyond)
+    assert beyond >= 1 and beyond == PARTS_BEYOND_256[name]
+    assert not any(st == "budget" for s in rt.BATCHES for p in rt.local_crash_case(name, s)[1] for _, st, _ in p)
+    low = rt.LOW_NODES
+    decides = behind = over = 0
+    for setting in rt.BATCHES:
+        _, parts, combined, _ = rt.local_crash_case(name, setting, low)
+        for p, (status, nodes) in zip(parts, combined):
+            sts = [st for _, st, _ in p]
+            assert all(nd == low for _, st, nd in p if st == "budget")
+            assert all(nd <= low for _, _, nd in p) and nodes == sum(nd for _, _, nd in p)
+            if status == "budget":              # the lowest part that is not lin is a `budget` one
+                assert all(st == "lin" for st in sts[:sts.index("budget")])
+                decides += 1
+            elif "budget" in sts:               # a `budget` part behind a lower failing key: the lower key's status
+                assert status in ("nonlin", "error") and sts.index(status) < sts.index("budget")
+                behind += 1
+            over += nodes > low
+    print(name, "at max_nodes", low, "- budget decides:", decides, "budget behind a lower key:", behind,
+          "summed nodes beyond it:", over)
+    assert decides >= 3 and behind >= 1 and over >= 1
+    assert (decides, behind, over) == LOW[name]
+
+
+@pytest.mark.parametrize("name", WALKS)
+def test_keyed_walks(name):
+    comp, K, _ = rt.keyed_spec(name)
+    m, sp, init = rt.model(comp), rt.spec(comp), rt.inits_of(name)
+    assert sp.high == "post" and K == 8
+    h, ends = rt.keyed_walk(name, rt.WALK_PER_KEY)
+    assert len(h) == 128 and len({pid for pid, _ in h}) == 128 and max(pid for pid, _ in h) == 127
+    assert [x[0] for _, (_, x) in h[:K]] == list(range(K))          # round-robin over the keys
+    for k in range(K):
+        s = init[k]
+        mine = [(pid, x[1]) for pid, (kind, x) in h if kind == "L" and x[0] == k]
+        assert [pid for pid, _ in mine] == list(range(k * rt.WALK_PER_KEY, (k + 1) * rt.WALK_PER_KEY))
+        for _, i in mine:
+            word = int(m.post[s, i])
+            assert word >> sp.nr == (1 << (32 - sp.nr)) - 1         # bits at and above n_resp
+            a = word & ~int(m.post_err[s, i]) & ((1 << sp.nr) - 1)
+            assert a == rt.allowed_bits(comp, s, i) and bin(a).count("1") >= 2
+            s = part_state(comp, s, i, (a & -a).bit_length() - 1)
+        assert s == ends[k]
+    hists, parts, combined, product = rt.walk_case(name)
+    assert hists[0] == h and parts[0] == [(k, "lin", rt.WALK_PER_KEY) for k in range(K)] and combined[0] == ("lin", 128)
+    assert product[0][:2] == ("lin", 128)
+    # the short walk: one completed operation the end state of the highest key does not allow
+    short, k, (i, r) = rt.failing_walk(name)
+    walk, ends = rt.keyed_walk(name, rt.SHORT_WALK)
+    assert hists[1] == short and short[:-2] == walk and k == K - 1
+    assert short[-2:] == [(K * rt.SHORT_WALK, ("L", (k, i))), (K * rt.SHORT_WALK, ("R", r))]
+    assert not (rt.allowed_bits(comp, ends[k], i) >> r) & 1 and not rt.tables_of(comp).err[ends[k], i, r]
+    assert [(key, st) for key, st, _ in parts[1]] == [(q, "lin") for q in range(K - 1)] + [(k, "nonlin")]
+    assert all(nd == rt.SHORT_WALK for _, _, nd in parts[1][:-1]) and rt.SHORT_WALK < parts[1][-1][2] < rt.MAX_NODES
+    assert combined[1] == ("nonlin", (K - 1) * rt.SHORT_WALK + parts[1][-1][2])
+    print(name, "the failing key's part:", parts[1][-1], "the product:", product[1][:2])
+
+
+def test_empty_allowed_words():
+    """Rule 2 where the allowed word is empty only after the `& symbols` cut
+    and post_err: a lone pending invocation there is `lin` with 0 nodes."""
+    assert not rt.empty_allowed("n_1inv") and not rt.empty_allowed("c_odd")
+    pairs = rt.empty_allowed("n_r2")
+    m, t = rt.model("n_r2"), rt.tables_of("n_r2")
+    assert len(pairs) >= 10
+    for s, i in pairs:
+        word = int(m.post[s, i])
+        assert word and not word & ~int(m.post_err[s, i]) & 3 and not (t.post[s, i] & ~t.err[s, i]).any()
+    assert any(int(m.post[s, i]) & int(m.post_err[s, i]) & 3 for s, i in pairs)     # some bit post_err removes
+    cases = rt.empty_allowed_histories("k8_r2")
+    assert not rt.empty_allowed_histories("k8_1inv")
+    init, c = rt.inits_of("k8_r2"), rt.closures("n_r2")
+    assert {s for s, _ in pairs} == {s for s, _, _, _ in cases} and any(s != 0 for s, _, _, _ in cases)
+    hists, parts, combined, product = rt.walk_case("k8_r2")
+    assert len(hists) == 2 + 3 * len(cases)
+    for n, (s, i, k, (h1, h2, h3)) in enumerate(cases):
+        assert init[k] == s and h1 == [(0, ("L", (k, i)))] and h2[:1] == h3[:1] == h1
+        assert hists[2 + 3 * n:5 + 3 * n] == [h1, h2, h3]
+        p1, p2, p3 = parts[2 + 3 * n:5 + 3 * n]
+        assert p1 == [(k, "lin", 0)] and klr.check(c, 8, h1, rt.MAX_NODES, init) == ("lin", 0)
+        k2 = h2[1][1][1][0]
+        assert k2 != k and sorted(p2) == sorted([(k, "lin", 0), (k2, "lin", 1)])
+        assert combined[3 + 3 * n] == ("lin", 1)
+        assert h3[1][1][1][0] == k and [key for key, _, _ in p3] == [k]
+        assert combined[4 + 3 * n] == klr.check(c, 8, h3, rt.MAX_NODES, init)
+    assert {c[0] for c in combined[2:]} == {"lin"} and {c[1] for c in combined[4::3]} >= {1, 2}
+
+
+def split_inputs(name):
+    c = rt.closures(name)
+    hists = [h for s in rt.BATCHES for h in rt.crashed(name, s)]
+    rng = random.Random(f"rawtables/split/{name}")
+    for setting, n in (("6x16", 60), (an.RANDOM, 100)):
+        some = an.batch(c, setting, n)
+        hists += some + [pr.crash(h, rng, rt.CRASH) for h in some]
+    return hists
+
+
+@pytest.mark.parametrize("name", ALL_KEYED)
+def test_split_history_pending_is_the_restatements_split(name):
+    comp, K, _ = rt.keyed_spec(name)
+    m, c, sp = rt.model(name), rt.closures(comp), rt.spec(comp)
+    reasons = collections.Counter()
+    differs = 0
+    for h in split_inputs(name):
+        want = klr.split(c, K, h)
+        reason = klr.refusal(c, K, h)
+        assert (want is None) == (reason is not None)
+        assert m.split_history(h, pending=True) == want, h
+        reasons[reason] += 1
+        plain = kref.split(c, K, h)                             # the default split is unchanged
+        assert m.split_history(h) == plain and m.split_history(h, pending=False) == plain, h
+        differs += plain != want
+    print(name, dict(reasons))
+    # the reasons an encodable history of at most 128 events can show, and splits of both kinds
+    assert reasons[None] >= sum(rt.BATCHES.values()) and reasons["lone_response"] and reasons["two_in_flight"]
+    assert differs > sum(rt.BATCHES.values()) // 3 and set(reasons) <= {None, "lone_response", "two_in_flight"}
+    # the others, made by hand
+    long = an.exactly(rt.histories(name, "6x24")[0], 129)
+    by_hand = {"too_long": long, "symbol": [(0, ("L", (0, 0))), (0, ("R", sp.nr))],
+               "key": [(0, ("L", (K, 0))), (0, ("R", 0))]}
+    assert set(by_hand) | {"lone_response", "two_in_flight"} == set(klr.REASONS)
+    for reason, h in by_hand.items():
+        assert klr.refusal(c, K, h) == reason and klr.split(c, K, h) is None
+        assert m.split_history(h, pending=True) is None and m.split_history(h) is None
+    assert klr.split(c, K, long[:128]) is not None and m.split_history(long[:128], pending=True) is not None
+
+
+@pytest.mark.parametrize("name", ["k_deep", "k_odd", "k_max"])
+def test_complete_histories_are_the_check_calls_local_mode(name):
+    comp, K, model0 = rt.keyed_spec(name)
+    c = rt.closures(comp)
+    for setting in rt.BATCHES:
+        for h in rt.histories(name, setting):
+            assert not pr.pending_invocations(h)
+            assert klr.check(c, K, h, rt.MAX_NODES, model0) == kref.check(c, K, h, rt.MAX_NODES, model0)
