@@ -407,23 +407,29 @@ constexpr int kProbeTabPass2 = 10;
 constexpr int kProbeTabClass = 11;      // 3 slots
 constexpr int kProbeTabHits = 14;       // 2 slots: pass 2's memo hits, lo / hi
 
-struct TableArgs {
+// The arguments of a table call, one layout for the three models: `Dev` is the
+// device table, `State` the model value (32 bits; keyed: key k's state in bits
+// 8k .. 8k + 7 of 64).  The three argument types are structs of their own, not
+// aliases, so that the kernels' names keep the type's name.
+template <class Dev, class State>
+struct TableArgsT {
     SearchArgs s;                 // histories, flags, max_nodes, time limit, outputs, buckets, timed_out
-    TableDev t;
-    uint32_t state0;              // the initial state (model0)
+    Dev t;
+    State state0;                 // the initial state (model0)
     uint32_t* cnt;                // TCnt
     uint32_t* class_list[3];      // n_hist entries each
     uint32_t* heavy_list[3];
     uint64_t budget;              // pass 1's node budget (0 = a single pass)
     qsmd_totals* totals;          // device
     uint32_t* probe_host;         // pinned
-    uint4* memo;                  // pass 2's state memo ("table_memo"): grid2 x 64 tables of memo_entries
-                                  // entries of 2 x uint4, or null (off: today's launches)
+    uint4* memo;                  // pass 2's state memo: grid2 x 64 tables of memo_entries entries (narrow
+                                  // and wide 2 x uint4, keyed 3 x uint4), or null (off: the plain pass 2)
     uint32_t memo_entries;        // a power of two
-    uint32_t memo_epoch;          // this call's tag (24 bits)
+    uint32_t memo_epoch;          // this call's tag (narrow 24 bits, wide 16, keyed a full word, never 0)
     uint8_t* path;                // the explain call's outputs (launch_table_explain), else null:
     uint4* explain;               // the witness layout; one qsmd_explain (16 B) per history
 };
+struct TableArgs : TableArgsT<TableDev, uint32_t> {};
 // bin + per class pass 1 (+ pass 2 when budget) + finish; grid1 / grid2: the
 // workgroups of each class's passes (any value >= 1 gives the same results);
 // classes: bit k set = launch class k
@@ -480,22 +486,7 @@ struct WTableDev {
 // TableArgs with the wide table; the workspace, the counters (TCnt) and the
 // probe slots are the narrow path's.  memo_epoch: 16 bits (the state has the
 // low 16 of the entry's tag word).
-struct WTableArgs {
-    SearchArgs s;
-    WTableDev t;
-    uint32_t state0;
-    uint32_t* cnt;
-    uint32_t* class_list[3];
-    uint32_t* heavy_list[3];
-    uint64_t budget;
-    qsmd_totals* totals;
-    uint32_t* probe_host;
-    uint4* memo;
-    uint32_t memo_entries;
-    uint32_t memo_epoch;
-    uint8_t* path;                // the explain call's outputs (launch_table_explain), else null:
-    uint4* explain;               // the witness layout; one qsmd_explain (16 B) per history
-};
+struct WTableArgs : TableArgsT<WTableDev, uint32_t> {};
 hipError_t launch_table(const WTableArgs& p, const uint32_t grid1[3], const uint32_t grid2[3], uint32_t classes,
                         hipStream_t s);
 hipError_t launch_table_explain(const WTableArgs& p, const uint32_t grid1[3], const uint32_t grid2[3],
@@ -507,24 +498,9 @@ hipError_t launch_table_explain(const WTableArgs& p, const uint32_t grid1[3], co
 // n_keys component states, key k's in byte k of a 64-bit word.  The
 // workspace, the counters (TCnt) and the probe slots are the narrow path's.
 // Pass 2's state memo is its own (knob "ktable_memo"): an entry holds the
-// 64-bit state, 3 x uint4 (ktable_host.h, ktable.hip KTableMemo).
-struct KTableArgs {
-    SearchArgs s;
-    TableDev t;                   // the component
+// 64-bit state, 3 x uint4 (ktable_host.h, table_search.h MemoEntry48).
+struct KTableArgs : TableArgsT<TableDev, uint64_t> {     // t: the component
     uint32_t n_keys;              // 1..QSMD_KTABLE_MAX_KEYS
-    uint64_t state0;              // the initial model: key k's state in bits 8k .. 8k + 7
-    uint32_t* cnt;
-    uint32_t* class_list[3];
-    uint32_t* heavy_list[3];
-    uint64_t budget;
-    qsmd_totals* totals;
-    uint32_t* probe_host;
-    uint4* memo;                  // pass 2's state memo ("ktable_memo"): grid2 x 64 tables of memo_entries
-                                  // entries of 3 x uint4, or null (off: the plain pass 2)
-    uint32_t memo_entries;        // a power of two
-    uint32_t memo_epoch;          // this call's tag: a full word, never 0
-    uint8_t* path;                // the explain call's outputs (launch_table_explain), else null:
-    uint4* explain;               // the witness layout; one qsmd_explain (16 B) per history
 };
 hipError_t launch_table(const KTableArgs& p, const uint32_t grid1[3], const uint32_t grid2[3], uint32_t classes,
                         hipStream_t s);

@@ -58,8 +58,8 @@ inline bool ktable_pack_state(const uint32_t* model0, uint32_t init, uint32_t n_
     return true;
 }
 
-// Pass 2's state memo on the keyed path (knob "ktable_memo", ktable.hip
-// KTableMemo): one direct-mapped table of `entries` entries per lane slot of
+// Pass 2's state memo on the keyed path (knob "ktable_memo", table_search.h
+// TableMemo with MemoEntry48): one direct-mapped table of `entries` entries per lane slot of
 // pass 2's grid.  One entry size for every width class: 3 x uint4 (count 64 |
 // epoch 32 | history 32, state 64 | rem words 0-1, rem words 2-3 | zero); the
 // 32- and 64-event classes never touch the third.

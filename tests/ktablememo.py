@@ -7,7 +7,7 @@ TEST INFRASTRUCTURE ONLY.
   :func:`klin_deep`, :func:`klock_deep`) and the table of their known answers
   (:data:`KDEEP`).  The answers are ``tablememo.exact_count`` on
   ``ktablegen.product(component, K)``: never the code under test.
-* :func:`kmemo_dfs` -- a literal mirror of ``KTableDFS::step<MEMO>``, which is
+* :func:`kmemo_dfs` -- a literal mirror of ``TableLane::check_step<KeyedModel, MEMO>``, which is
   ``tablememo.memo_dfs`` with the 64-bit packed state (key k in bits 8k ..
   8k + 7), the kernel's slot hash over both state words, and a lossy
   direct-mapped table.  ``state_mask`` weakens the memo's key (hash and hit
@@ -117,14 +117,14 @@ def exact(name, max_nodes=0, stats=None):
 
 
 # ---------------------------------------------------------------------------
-# kmemo_dfs: KTableDFS::step<MEMO>, literally
+# kmemo_dfs: TableLane::check_step<KeyedModel, MEMO>, literally
 # ---------------------------------------------------------------------------
 
 HASH_S = (0x165667B1, 0xD6E8FEB9)       # the state's low and high word
 
 
 def kmemo_slot(rem, n_words, state, entries):
-    """The kernel's slot hash (ktable.hip KTableMemo::slot_of)."""
+    """The kernel's slot hash (table_search.h TableMemo::slot_of, 64-bit state)."""
     x = ((state & 0xFFFFFFFF) * HASH_S[0]) & 0xFFFFFFFF
     x ^= ((state >> 32) * HASH_S[1]) & 0xFFFFFFFF
     for k in range(n_words):

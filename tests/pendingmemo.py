@@ -10,7 +10,7 @@ TEST INFRASTRUCTURE ONLY.
   ``findResponse``, else one child per ``pending_ref.allowed`` symbol, counted
   but not tested), plain ``any`` at the root, ``any'`` below, and the rule of
   the root without a child in a history without a response.
-* :func:`pending_memo_dfs` -- a literal mirror of ``PendingDFS::step<MEMO>``:
+* :func:`pending_memo_dfs` -- a literal mirror of ``TableLane::pending_step<MEMO>`` (csrc/table_search.h):
   Lemma L1 bitsets, one child per iteration, the resume of an assumed level at
   its next allowed symbol, a lossy direct-mapped table of ``entries`` entries
   with the kernel's slot hash (``tablememo.memo_slot``).
@@ -112,7 +112,7 @@ def exact_count_pending(model, hist, max_nodes=0, stats=None):
 
 
 # ---------------------------------------------------------------------------
-# pending_memo_dfs: PendingDFS::step<MEMO>, literally
+# pending_memo_dfs: TableLane::pending_step<MEMO>, literally
 # ---------------------------------------------------------------------------
 
 def _ctz(x):

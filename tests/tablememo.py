@@ -9,7 +9,7 @@ TEST INFRASTRUCTURE ONLY.
   below (src/Linearisability.hs:61, :67-69).  Independent of the kernel's
   bitset formulation: it removes events from a tuple the way ``filter1`` and
   ``findResponse`` do.
-* :func:`memo_dfs` -- a literal mirror of ``TableDFS::step`` with the memo
+* :func:`memo_dfs` -- a literal mirror of ``TableLane::check_step`` (csrc/table_search.h) with the memo
   rule: Lemma L1 bitsets, one candidate per iteration, a lossy direct-mapped
   table of ``entries`` entries with the kernel's slot hash.
 * the deep histories of the GPU tests (:func:`reads`, :func:`lin_deep`,
@@ -103,7 +103,7 @@ def exact_count(model, hist, max_nodes=0, stats=None):
 
 
 # ---------------------------------------------------------------------------
-# memo_dfs: TableDFS::step, literally
+# memo_dfs: TableLane::check_step, literally
 # ---------------------------------------------------------------------------
 
 @functools.lru_cache(maxsize=None)
@@ -118,7 +118,7 @@ HASH_K = (0x9E3779B1, 0x85EBCA77, 0xC2B2AE3D, 0x27D4EB2F)
 
 
 def memo_slot(rem, n_words, state, entries):
-    """The kernel's slot hash (table.hip TableMemo::slot_of)."""
+    """The kernel's slot hash (table_search.h TableMemo::slot_of)."""
     x = (state * 0x165667B1) & 0xFFFFFFFF
     for k in range(n_words):
         x ^= (((rem >> (32 * k)) & 0xFFFFFFFF) * HASH_K[k]) & 0xFFFFFFFF

@@ -1,5 +1,5 @@
 """The CPU references of the keyed path's state memo (tests/ktablememo.py):
-the literal mirror of ``KTableDFS::step<MEMO>`` against the exact count on the
+the literal mirror of ``TableLane::check_step<KeyedModel, MEMO>`` against the exact count on the
 product closures for every deep row the GPU tests run
 (tests/test_gpu_ktable_memo.py), the run-time cap of those rows, the teeth of
 the inputs (a memo keyed on part of the state gets them wrong), and the sizing
